@@ -51,6 +51,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 HUB_CLOCK_HZ = 2.4e9         # MI355X peak engine clock: cycles of the `chain` bound (also.AM32)
 COLS_PER_GPU = 128
+DUMP_BUDGET_BYTES = 56 << 20      # --dump-outputs: bytes of C written at most (the row indices beside them stay under 64 MB in all)
+DUMP_SEED = 126                   # --dump-outputs: the row sample of a C larger than the budget
 
 # The contract: rank 0 prints ONE JSON line on stdout.  Libraries write there too (RCCL prints a five-line version banner to stdout at
 # communicator set-up on this image), so main() points file descriptor 1 at stderr for the whole run and the line goes out through
@@ -100,6 +102,10 @@ def parse():
     ap.add_argument("--cpu-rows", type=int, default=None, help="rows of the workload the CPU baseline runs (default: all for C1)")
     ap.add_argument("--check", action="store_true", help="verify a row sample against the oracle after timing")
     ap.add_argument("--sweep", default=None, help="tuning sweep name: knobs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the C of the last timed step as DIR/C_sample.npy (float32 rows of C, all of them "
+                         "when C fits in DUMP_BUDGET_BYTES, otherwise a fixed seeded sample) and DIR/C_sample_rows.npy (their row indices, "
+                         "float64): two builds run with the same arguments can be compared output for output")
     ap.add_argument("--rehearse-multi", action="store_true",
                     help="run the N>1 code path (RCCL group, panel pipeline, breakdown legs) with a world of 1 on one GPU")
     return ap.parse_args()
@@ -418,6 +424,8 @@ def main():
         elapsed = time.perf_counter() - t0
         if multi:
             elapsed = agree(elapsed, dist.ReduceOp.MAX)
+        if args.dump_outputs and rank == 0 and args.steps > 0:
+            R["outputs"] = sample_outputs(d_Cfull)          # outside the timed region: what the last timed step left in C
         dev_ms = [a.elapsed_time(b) for a, b in ev]
         return {"ms_per_step": elapsed * 1e3 / max(1, args.steps), "dev_ms_mean": float(np.mean(dev_ms)) if dev_ms else float("nan")}
 
@@ -425,7 +433,7 @@ def main():
     flops_total = 2.0 * nnz * n_total
     # everything the line is built from; filled in as the run goes, so that a line can be printed at any point after the first timing
     R = {"timing": None, "exchange": exchange, "tuning": None, "ref_protocol_ms": None, "also": None, "check": None, "breakdown": None,
-         "strong_ref": None, "cpu": None, "safe_timing": None}
+         "strong_ref": None, "cpu": None, "safe_timing": None, "outputs": None}
 
     def build_line():
         ms_per_step, dev_ms_mean = R["timing"]["ms_per_step"], R["timing"]["dev_ms_mean"]
@@ -770,6 +778,9 @@ def main():
     if rank == 0 and not multi and not args.no_cpu_baseline:
         R["cpu"] = cpu_baseline(args, ptr, idx, vals, B_loc, M, n_loc)
 
+    if rank == 0 and R["outputs"] is not None:
+        write_outputs(args.dump_outputs, R["outputs"])
+
     if rank == 0:
         if wd is not None:
             wd.set_line(None)          # the final line is printed here, once
@@ -779,6 +790,29 @@ def main():
         del sharded
         dist.destroy_process_group()
         wd.disarm()
+
+
+def sample_outputs(d_C):
+    """--dump-outputs: rows of the device matrix C (row-major M x N) on the host -- all of them when C fits in DUMP_BUDGET_BYTES,
+    otherwise a seeded sample (the same rows for the same M and N on every run), in ascending order."""
+    import torch
+
+    M, N = d_C.shape
+    keep = min(M, DUMP_BUDGET_BYTES // max(1, 4 * N))
+    if keep == M:
+        rows = np.arange(M, dtype=np.int64)
+        C = d_C.cpu().numpy()
+    else:
+        g = np.random.Generator(np.random.Philox(key=[DUMP_SEED, 0]))
+        rows = np.sort(g.choice(M, size=keep, replace=False)).astype(np.int64)
+        C = d_C.index_select(0, torch.from_numpy(rows).to(d_C.device)).cpu().numpy()
+    return {"C_sample": np.ascontiguousarray(C, dtype=np.float32), "C_sample_rows": rows.astype(np.float64)}
+
+
+def write_outputs(path, outputs):
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cache_resident_roofline(model, ms, traffic, src, M, n, launches):

@@ -73,6 +73,35 @@ def test_single_gpu_line():
     assert also["LONG_ROWS"]["options"]["n_col_strips"] >= 1 and also["LONG_ROWS"]["options"]["n_medium_rows"] > 0
 
 
+def test_dump_outputs_is_the_timed_steps_c(tmp_path):
+    """--dump-outputs DIR: the C the timed steps computed, as float32 rows with their indices (float64).  A C above the byte
+    budget (here 64 MiB) is a seeded row sample, the same rows on every run; each sampled row equals the oracle's bit for bit."""
+    import argparse
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import oracle
+
+    d = _run("--N", "256", "--no-also", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "out"))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0
+    C = np.load(tmp_path / "out" / "C_sample.npy")
+    rows = np.load(tmp_path / "out" / "C_sample_rows.npy")
+    assert C.dtype == np.float32 and rows.dtype == np.float64
+    assert C.nbytes + rows.nbytes <= 64 * 10**6
+    assert C.shape == (bench.DUMP_BUDGET_BYTES // (4 * 256), 256) and rows.shape == (C.shape[0],)
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 65536
+    a = argparse.Namespace(mode="weak", N=256, M=65536, config="C1")
+    _, M, _, _, ptr, idx, vals, B = bench.build_inputs(a, 1, 0)
+    r = rows.astype(np.int64)
+    deg = np.diff(ptr)[r]
+    sp = np.concatenate([[0], np.cumsum(deg)]).astype(np.int32)
+    take = np.concatenate([np.arange(ptr[i], ptr[i + 1]) for i in r])
+    exp = oracle.spmm_omp(sp, idx[take], vals[take], B)
+    assert np.array_equal(C.view(np.uint32), exp.view(np.uint32))
+
+
 @pytest.mark.parametrize("exchange", ["allgather", "direct", "peer2d", "peer_store"])
 def test_multi_gpu_path_rehearsal(exchange):
     d = _run("--rehearse-multi", "--no-cpu-baseline", "--check", "--panels", "3", "--exchange", exchange)
