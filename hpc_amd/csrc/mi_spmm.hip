@@ -26,6 +26,27 @@ using namespace mi;
 
 #define HIP_TRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return (int)e_; } while (0)
 
+// The seven settings "autotune" may choose (0 = auto everywhere but fused_step, whose auto is 2).  The handle holds two copies: `user`, what set_option
+// wrote, and `in_force`, what the plan and run_part use -- the caller's values, with the tuner's candidate or winner where the caller left one at auto.
+struct Tunables {
+    int64_t hub_thr;      // "long_row_threshold": rows longer than this are hubs (the resolved value in force: mi_spmm_handle::long_thr)
+    int64_t medium_thr;   // "medium_row_threshold": rows longer than this (and not hubs) run as one exact segment in the segment kernel
+    int64_t col_strips;   // "col_strips": column strips of the exact segments (plan.hpp): 1 = off, S >= 2 = that many (if the segments' columns ascend)
+    int64_t tile_cols;    // "tile_cols": widest column tile of the rows/segment kernels: 256 (whole wave on a row), 128, 64, 32
+    int64_t fused_step;   // "fused_step": 2 = auto, 0 = never, 1 = whenever the step is eligible: hub rows, segments and short rows as the three
+                          // roles of ONE launch (spmm_kernels.hpp spmm_small_step) instead of 2-3 launches and a side-stream fork / join
+    int64_t seg_order;    // "segment_order": 1 = segments longest first, 2 = in row order
+    int64_t rows_unroll;  // "rows_unroll": B-row gathers in flight per lane group in the rows kernel: 8, 16
+};
+
+// "autotune_mask" (mi_spmm.h): bit 0 tile, 1 strips, 2 medium, 3 fused, 4 segment order, 5 rows unroll, 6 hub threshold -- the settings the tuner changed
+static uint32_t tuned_settings(const Tunables &user, const Tunables &f)
+{
+    return (f.tile_cols != user.tile_cols ? 1u : 0u) | (f.col_strips != user.col_strips ? 2u : 0u) | (f.medium_thr != user.medium_thr ? 4u : 0u) |
+           (f.fused_step != user.fused_step ? 8u : 0u) | (f.seg_order != user.seg_order ? 16u : 0u) | (f.rows_unroll != user.rows_unroll ? 32u : 0u) |
+           (f.hub_thr != user.hub_thr ? 64u : 0u);
+}
+
 struct mi_spmm_handle {
     uint32_t magic;
     const int32_t *d_ptr;
@@ -34,9 +55,8 @@ struct mi_spmm_handle {
     int32_t num_v, num_cols, feat;
     int64_t nnz;
     // options
-    int64_t long_thr_user;  // what the caller asked for (0 = auto); long_thr holds the resolved value
-    int64_t medium_thr;  // rows longer than this (and not split) run as one exact segment in the segment kernel; 0 = auto
-    int64_t medium_res;  // the value in force after preprocess (auto resolved, capped by long_thr)
+    Tunables user, in_force;
+    int64_t medium_res;  // the medium threshold in force after preprocess (auto resolved, capped by long_thr)
     int64_t split_long;   // 0 (default): hubs keep their stored order (spmm_hub); 1: hubs are cut into pieces summed piece by piece
     int64_t hub_slice;    // columns per hub wave: 16, 32, 64; 0 = auto
     int64_t hub_overlap;  // 1 (default): the hub kernel and the segment kernel run on handle-owned side streams, forked from and joined
@@ -49,24 +69,19 @@ struct mi_spmm_handle {
     hipEvent_t ev_fork, ev_join[2];
     bool fork_recorded, forked[2];   // state of the current run_rows call
     bool overlap_on[2];   // resolved by preprocess: is the fork/join (~20 us of launch latency per call) worth it for this class
-    int64_t long_thr, long_chunk, rows_per_block, xcd_remap, nt_store, nt_stream, block_path;
+    int64_t long_thr;     // the hub threshold in force (resolved by preprocess; before it, the caller's value)
+    int64_t long_chunk, rows_per_block, xcd_remap, nt_store, nt_stream, block_path;
     int64_t block_threads;  // v2 workgroup size: 64, 128 or 256
     int64_t gpu_preprocess;  // 1: segment table built on the device (default); 0: reference-style host loop
     int64_t kernel;  // 2 = spmm_rows_v2 (pipelined items); 1 named the first-generation kernel, retired in round 3
     int64_t split_cols;  // 1 (default): columns past the last full 256-column tile get their own launches
     int64_t segment_unroll;  // B-row gathers in flight per lane group in the segment kernel: 8, 16 or 32 (default)
-    int64_t tile_cols;       // widest column tile of the rows/segment kernels: 256 (whole wave on a row), 128, 64, 32; 0 = auto
-    int64_t col_strips;      // column strips of the exact segments (plan.hpp): 0 = auto, 1 = off, S >= 2 = that many (if the segments' columns ascend)
     Chunk *d_strips;         // [n_strips][n_chunks] sub-segments, strip-major; grow-only buffer (capacity strips_cap sub-segments), kept across preprocess calls
     size_t strips_cap;
     int32_t n_strips;        // strips in force (1 = none)
     int32_t seg_unsorted;    // segments whose columns do not ascend (-1: not looked at)
     int64_t seg_nnz;         // nonzeros in the whole segments (either plan builder): the strip rule's input, known before any column is read
     int64_t strips_builder;  // 0 (default): strip_segments, one pass; 1: the round-4 pair survey_segments + build_col_strips (cross-check)
-    int64_t seg_order;       // "segment_order": 0 = auto, 1 = segments longest first, 2 = in row order
-    int64_t rows_unroll;     // "rows_unroll": B-row gathers in flight per lane group in the rows kernel: 0 = auto, 8, 16
-    int64_t fused_step;      // "fused_step": 2 (default) = auto, 0 = never, 1 = whenever the step is eligible: hub rows, segments and short rows as the three
-                             // roles of ONE launch (spmm_kernels.hpp spmm_small_step) instead of 2-3 launches and a side-stream fork / join
     int32_t last_fused;      // 1: the last run call went through the small-step kernel
     int64_t fused_order;     // "fused_order": 0 (default) = auto, 1 = hub workgroups first in the small-step grid, 2 = segment workgroups first
     int32_t last_seg_first;  // 1: the last small-step launch put its segment workgroups first
@@ -74,9 +89,8 @@ struct mi_spmm_handle {
     // "autotune" (round 5): the rules above are guesses from a 8 192-row sample and a histogram; a wrong guess is silent (same bits, slower).  With the option on,
     // preprocess MEASURES: the step is timed on the buffers it is given (the reference's preprocess touches vout too: spmm_opt.cu:67) under the auto plan and
     // under a handful of forced settings of the options the caller left to us -- tile width, strip count, medium threshold, one launch or several -- and the
-    // fastest is kept.  Scheduling only: whatever wins gives the same bits.
+    // fastest is kept (in_force; user is never touched).  Scheduling only: whatever wins gives the same bits.
     int64_t autotune;
-    uint32_t tuned_mask;     // options the tuner set (bit 0 tile_cols, 1 col_strips, 2 medium_thr, 3 fused_step, 4 segment_order, 5 rows_unroll, 6 long_row_threshold): back to auto before the next tuning
     int32_t tune_evals;      // candidate settings timed by the last preprocess
     double tune_auto_ms, tune_best_ms;
     // plan
@@ -91,7 +105,7 @@ struct mi_spmm_handle {
     int32_t local_pct;   // column locality sample (percent); -1 = not measured
     int32_t front_pct;   // sampled nonzeros in the first quarter of the columns (percent; uniform columns: 25)
     double preprocess_us;
-    double phase_us[5];  // d2h row_ptr + validate, column check, block detection, host segment table, upload
+    double phase_us[5];  // set-up, column check, block detection, plan tables (either builder, strips, rebuild), partial sums + block items
     int32_t last_lpr, last_v, last_launches, last_wide;
     // block (MFMA) path
     int64_t block_min_len;
@@ -401,8 +415,8 @@ static int ensure_side_streams(mi_spmm_handle *h)
     // A fork + join costs ~20 us of launch latency per run call (ddi-shaped N = 32: 0.047 -> 0.069 ms): worth it once the
     // step is long enough to hide something behind (estimate >= 0.2 ms) or the longest hub alone is a 50 us chain.
     // "hub_overlap": 0 = never, 1 = this rule, 2 = always.
-    const double bytes = (double)h->nnz * (4.0 * h->feat + 8.0) + 4.0 * (double)h->num_v * h->feat;
-    const bool long_step = bytes / 6e12 >= 200e-6;
+    constexpr double kFabricRate = 6e12;
+    const bool long_step = gather_bytes(h->nnz, h->num_v, h->feat) / kFabricRate >= 200e-6;
     const bool exact_hubs = h->n_long > 0 && !h->split_long;
     h->overlap_on[0] = exact_hubs && (h->hub_overlap == 2 || (h->hub_overlap == 1 && (long_step || h->max_row_nnz >= 7000)));
     // The segment kernel gets a side stream of its own only where that was measured to pay (interleaved A/B over twelve graph shapes x three widths,
@@ -455,7 +469,8 @@ static int plan_col_strips(mi_spmm_handle *h)
 {
     h->n_strips = 1;
     h->seg_unsorted = -1;
-    if (h->col_strips == 1 || h->n_chunks <= 0 || h->split_long || h->n_slots > 0 || h->feat <= 0 || h->num_cols < 2) return MI_SPMM_OK;
+    const int64_t want = h->in_force.col_strips;
+    if (want == 1 || h->n_chunks <= 0 || h->split_long || h->n_slots > 0 || h->feat <= 0 || h->num_cols < 2) return MI_SPMM_OK;
     // width of a column tile of the segment kernel at this handle's N (run_part: lane groups of N/4 lanes, capped by the tile rule)
     const int V = h->feat >= 4 ? 4 : 1;
     int lpr = 1;
@@ -469,8 +484,8 @@ static int plan_col_strips(mi_spmm_handle *h)
     //  once the rows are long: protein- / reddit-community (58 - 60 % local) 0.57 - 0.67 of the time with strips, and a BANDED matrix of 300-700-nonzero rows
     //  (100 % local: a row sits inside one or two strips) 0.54 - 0.69 -- the segment table is sorted by length, so a launch's rows come from all over the band.
     //  The gate is gone: profiles/r05_regret.md.)
-    if (h->col_strips == 0 && h->local_pct >= 95) return MI_SPMM_OK;      // banded / mesh: the rows stay in the rows kernel (medium rule), nothing long is left to strip
-    if (h->col_strips == 0 && resolve_col_strips(h->num_cols, tile, h->nnz, h->n_chunks, h->nnz, h->front_pct, h->local_pct) < 2) return MI_SPMM_OK;   // cannot pay whatever the survey says
+    if (want == 0 && h->local_pct >= 95) return MI_SPMM_OK;      // banded / mesh: the rows stay in the rows kernel (medium rule), nothing long is left to strip
+    if (want == 0 && resolve_col_strips(h->num_cols, tile, h->nnz, h->n_chunks, h->nnz, h->front_pct, h->local_pct) < 2) return MI_SPMM_OK;   // cannot pay whatever the survey says
     if (!h->d_col_bad) HIP_TRY(hipMalloc((void **)&h->d_col_bad, 256));
     void *d_sv = (char *)h->d_col_bad + 64;            // (the first bytes hold the column-range flag a second plan reads again)
     SegmentSurvey sv;
@@ -481,14 +496,15 @@ static int plan_col_strips(mi_spmm_handle *h)
         if (sv.unsorted) return MI_SPMM_OK;            // a row whose columns do not ascend cannot be cut by column without changing its order
         if ((int64_t)sv.nnz != h->seg_nnz) return MI_SPMM_ESTATE;      // the plan builders' count and the survey's are the same number
     }
-    int64_t S = h->col_strips >= 2 ? h->col_strips : resolve_col_strips(h->num_cols, tile, h->seg_nnz, h->n_chunks, h->nnz, h->front_pct, h->local_pct);
+    int64_t S = want >= 2 ? want : resolve_col_strips(h->num_cols, tile, h->seg_nnz, h->n_chunks, h->nnz, h->front_pct, h->local_pct);
     // local columns at a narrow B: a long row's nonzeros cluster in one or two strips, the other launches find it empty -- many strips only add launches
     // (ppa-community kLen 32: 14 strips DOUBLED the step, 4 are neutral, 2 take a fifth off; reddit- / protein-community kLen 32: 2 - 4 strips 0.88 - 0.95 of the time, 6 the same as none)
-    if (h->col_strips == 0 && h->local_pct >= 50 && h->feat < 128 && S > 2) S = 2;
+    if (want == 0 && h->local_pct >= 50 && h->feat < 128 && S > 2) S = 2;
     // a strip is a launch: ~10 us of ramp each.  Not more strips than the step has 0.1 ms slices of work (hold-out: an R-MAT of scale 18 at kLen 32 -- 0.17 ms
     // of bytes -- lost 30 % to six strips; every fitted case has >= 0.14 ms per strip)
-    if (h->col_strips == 0) {
-        const double step = ((double)h->nnz * (4.0 * h->feat + 8.0) + 4.0 * (double)h->num_v * h->feat) / 6e12;
+    if (want == 0) {
+        constexpr double kFabricRate = 6e12;
+        const double step = gather_bytes(h->nnz, h->num_v, h->feat) / kFabricRate;
         const int64_t by_time = (int64_t)(step / 100e-6);
         if (S > by_time) S = by_time;
     }
@@ -517,10 +533,186 @@ static int plan_col_strips(mi_spmm_handle *h)
     return MI_SPMM_OK;
 }
 
-// preprocess with no host pass over the rows: column check, block detection, classification, scans,
-// segment emission and the length sort all run on the device; one small copy comes back.
-static int preprocess_on_gpu(mi_spmm_handle *h, std::chrono::steady_clock::time_point t0)
+// The hub threshold a plan builder is given, from a setting: the caller's "long_row_threshold", a tuner's candidate, or the fold's 1 << 30.  Rows up to
+// it stay ONE exact segment of the segment kernel; longer ones (hubs) go to the hub kernel (stored order) or, with "split_long_rows", are cut into pieces.
+//   an explicit value is taken as is;
+//   auto, split mode: 2048 once there is enough work to hide a 2048-nonzero segment (nnz >= 2^24), proportionally lower for small matrices
+//     (profiles/r01_thresholds.txt);
+//   auto, exact mode: 0 -- the builder resolves it from the row-length histogram (plan.hpp resolve_hub_threshold).
+// The hub kernel moves 16-byte parts of B rows: in exact mode a B narrower than one part keeps its long rows as single exact segments of the segment
+// kernel, whatever the setting (slow on a real hub, but N < 4 has no bandwidth to speak of either way).
+static int64_t hub_threshold_for(const mi_spmm_handle *h, int64_t setting)
 {
+    if (!h->split_long && h->feat < 4) return INT32_MAX;
+    if (setting > 0) return setting;
+    if (!h->split_long) return 0;
+    const int64_t t = h->nnz / 8192;
+    return t < 256 ? 256 : (t > 2048 ? 2048 : t);
+}
+
+// The reference-style host loop ("gpu_preprocess" = 0), kept as the cross-check of build_plan_gpu (preprocess_gpu.hip): the same PlanOut from row_ptr
+// copied back -- validation, histogram, column sample, the two threshold rules, classification, sort, upload.  The segment table is the reference's Task
+// list (spmm_opt.cu:43-54), kept only for rows that need it:
+//   len > thr                 -> hub: listed (exact mode) or cut into pieces of clen nonzeros, partial sums + ordered reduce (split mode)
+//   mthr < len <= thr         -> ONE segment = the whole row, stored straight to C (exact order)
+// Rows of block-path groups are excluded.  Segments are sorted longest first: neighbours in a wave have similar lengths and the tail is short.
+static int build_plan_host(const int32_t *d_row_ptr, const int32_t *d_col_idx, int32_t M, int32_t K, int32_t N, int64_t nnz,
+                           const uint8_t *d_blk_flag, const unsigned int *d_col_bad, int32_t mthr_user, int32_t thr_user, int32_t clen, int32_t split,
+                           int32_t seg_order, void *d_scratch256, PlanOut *out)
+{
+    *out = PlanOut();
+    std::vector<int32_t> ptr((size_t)M + 1);
+    HIP_TRY(hipMemcpy(ptr.data(), d_row_ptr, sizeof(int32_t) * ((size_t)M + 1), hipMemcpyDeviceToHost));
+    unsigned int col_bad = 0;
+    if (d_col_bad) HIP_TRY(hipMemcpy(&col_bad, d_col_bad, sizeof(col_bad), hipMemcpyDeviceToHost));
+    // data.cu:40-45 asserts ptr[num_v] == num_e; monotone rows and in-range columns keep the kernels in bounds
+    if (col_bad || ptr[0] < 0 || (int64_t)ptr[M] != nnz) return MI_SPMM_ECSR;
+    LenHist hist;
+    std::memset(&hist, 0, sizeof(hist));
+    int32_t max_len = 0;
+    for (int32_t r = 0; r < M; ++r) {
+        const int32_t len = ptr[r + 1] - ptr[r];
+        if (len < 0) return MI_SPMM_ECSR;
+        if (len > max_len) max_len = len;
+        for (int i = 0; i < kHistN && len > hist_threshold(i); ++i) { ++hist.cnt[i]; hist.nnz[i] += (unsigned long long)len; }
+    }
+    const int src = sample_columns_gpu(d_row_ptr, d_col_idx, M, K, nnz, d_scratch256, &out->local_pct, &out->front_pct);
+    if (src != 0) return src;
+    const int32_t thr = thr_user > 0 ? thr_user : resolve_hub_threshold(nnz, M, K, N, hist.nnz, max_len);
+    const int32_t mthr = resolve_medium_threshold(mthr_user, nnz, M, max_len, thr, out->local_pct, N);
+    out->max_len = max_len;
+    out->thr = thr;
+    out->mthr = mthr;
+    std::vector<uint8_t> flags;
+    if (d_blk_flag) {
+        flags.resize((size_t)(M + 15) / 16);
+        HIP_TRY(hipMemcpy(flags.data(), d_blk_flag, flags.size(), hipMemcpyDeviceToHost));
+        std::vector<int32_t> groups;
+        for (size_t g = 0; g < flags.size(); ++g) if (flags[g]) groups.push_back((int32_t)g);
+        if (!groups.empty()) {
+            if (hipMalloc((void **)&out->d_blk_groups, groups.size() * sizeof(int32_t)) != hipSuccess) return MI_SPMM_ENOMEM;
+            HIP_TRY(hipMemcpy(out->d_blk_groups, groups.data(), groups.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+            out->n_blk_groups = (int32_t)groups.size();
+        }
+    }
+    std::vector<Chunk> chunks;
+    std::vector<LongRow> longs;
+    for (int32_t r = 0; r < M && max_len > mthr; ++r) {
+        const int32_t beg = ptr[r], end = ptr[r + 1], len = end - beg;
+        if (len <= mthr) continue;
+        if (out->n_blk_groups > 0 && flags[(size_t)(r >> 4)]) continue;      // block path owns it, whatever its length
+        if (len <= thr) {
+            chunks.push_back(Chunk{beg, end, -1, r});
+            ++out->n_medium;
+            out->seg_nnz += len;
+            continue;
+        }
+        LongRow L{r, -1, 0, len};         // exact order: the hub kernel walks the row whole
+        if (split) {
+            L.first_slot = out->n_slots;
+            for (int32_t b = beg; b < end; b += (end - b > clen ? clen : end - b)) {
+                chunks.push_back(Chunk{b, (end - b > clen) ? b + clen : end, out->n_slots++, r});
+                ++L.n_chunks;
+            }
+        }
+        longs.push_back(L);
+    }
+    // hub rows longest first, ties in row order (as the device builder's stable radix sort leaves them)
+    std::stable_sort(longs.begin(), longs.end(), [](const LongRow &x, const LongRow &y) { return x.len > y.len; });
+    // segments longest first, stable -- unless the row order was asked for
+    if (seg_order != 2) std::stable_sort(chunks.begin(), chunks.end(), [](const Chunk &x, const Chunk &y) { return x.end - x.beg > y.end - y.beg; });
+    out->n_chunks = (int32_t)chunks.size();
+    out->n_long = (int32_t)longs.size();
+    if (chunks.empty() && longs.empty()) return MI_SPMM_OK;
+    const size_t cb = chunks.size() * sizeof(Chunk), lb = longs.size() * sizeof(LongRow);
+    if (hipMalloc((void **)&out->d_chunks, cb ? cb : sizeof(Chunk)) != hipSuccess || hipMalloc((void **)&out->d_long, lb ? lb : sizeof(LongRow)) != hipSuccess)
+        return MI_SPMM_ENOMEM;
+    if (cb) HIP_TRY(hipMemcpy(out->d_chunks, chunks.data(), cb, hipMemcpyHostToDevice));
+    if (lb) HIP_TRY(hipMemcpy(out->d_long, longs.data(), lb, hipMemcpyHostToDevice));
+    return MI_SPMM_OK;
+}
+
+// The plan tables for one hub threshold (0 = auto) and one medium threshold (0 = auto), from the builder "gpu_preprocess" selects, then the column strips
+// of their segments.
+static int build_tables(mi_spmm_handle *h, int64_t thr, int64_t mthr_want)
+{
+    const int32_t mthr = (int32_t)((thr == 0 || mthr_want < thr) ? mthr_want : thr);
+    const unsigned int *d_bad = h->nnz > 0 ? h->d_col_bad : nullptr;
+    PlanOut po;
+    const int rc = h->gpu_preprocess
+        ? build_plan_gpu(h->d_ptr, h->d_idx, h->num_v, h->num_cols, h->feat, h->nnz, h->d_blk_flag, d_bad, mthr, (int32_t)thr, (int32_t)h->long_chunk,
+                         (int32_t)h->split_long, (int32_t)h->in_force.seg_order, &h->scratch_a, &h->scratch_b, &po)
+        : build_plan_host(h->d_ptr, h->d_idx, h->num_v, h->num_cols, h->feat, h->nnz, h->d_blk_flag, d_bad, mthr, (int32_t)thr, (int32_t)h->long_chunk,
+                          (int32_t)h->split_long, (int32_t)h->in_force.seg_order, h->d_col_bad ? (char *)h->d_col_bad + 64 : nullptr, &po);
+    h->d_chunks = po.d_chunks;
+    h->d_long = po.d_long;
+    h->d_blk_groups = po.d_blk_groups;
+    if (rc != 0) return rc;
+    h->n_chunks = po.n_chunks;
+    h->n_long = po.n_long;
+    h->n_slots = po.n_slots;
+    h->n_medium = po.n_medium;
+    h->n_blk_groups = po.n_blk_groups;
+    h->max_row_nnz = po.max_len;
+    h->medium_res = po.mthr;
+    h->long_thr = po.thr;
+    h->local_pct = po.local_pct;
+    h->front_pct = po.front_pct;
+    h->seg_nnz = po.seg_nnz;
+    return plan_col_strips(h);
+}
+
+// Drops the segment, hub and block-group tables of a plan that is built again (the block flags stay: detection does not depend on the plan).
+static void drop_tables(mi_spmm_handle *h)
+{
+    if (h->d_chunks) (void)hipFree(h->d_chunks);
+    if (h->d_long) (void)hipFree(h->d_long);
+    if (h->d_blk_groups) (void)hipFree(h->d_blk_groups);
+    h->d_chunks = nullptr;
+    h->d_long = nullptr;
+    h->d_blk_groups = nullptr;
+    h->ws_bytes = 0;
+}
+
+// What the plan just built asks for, once its strips are known.
+enum class Rebuild { kKeep, kFoldHubs, kKeepRows, kUnfold };
+static int32_t keep_rows_to(const mi_spmm_handle *h) { return h->feat >= 128 ? 1024 : 512; }
+static Rebuild next_plan(const mi_spmm_handle *h, bool folded)
+{
+    // The fold lost its strips (the folded plan surveys the former hub rows for the first time; if one of them has non-ascending columns, or the
+    // rule on the new survey says no strips, a 10^4-nonzero row would run as ONE unstripped segment chain): back to the plan with hubs, this time to be kept.
+    if (folded) return h->n_strips <= 1 ? Rebuild::kUnfold : Rebuild::kKeep;
+    const Tunables &f = h->in_force;
+    const int32_t M = h->num_v;
+    // Strips in force and a hub threshold that was ours to choose: a plan WITHOUT hubs when the longest row's sub-chains would hide inside the strips'
+    // launches -- as stripped segments those rows gather out of L2 like the rest, where the hub kernel gathers them out of all of B beside the strip
+    // launches (reddit-shaped N = 128 / 256: 5.07 -> 4.46, 8.97 -> 8.15 ms).  The longest row's chain, at 100 ns per nonzero over all strips, has to fit
+    // into half of the stripped step's estimate: at N = 32 the same graph's 20 758-nonzero row would be the step (1.08 -> 1.70 ms) and protein-shaped
+    // N = 32 loses 7 % (0.72 -> 0.78): both keep their hubs.  profiles/r04_col_strips.txt section 8
+    constexpr double kStrippedRate = 12e12;     // a stripped step: about twice the gather model's rate
+    const double step_s = gather_bytes(h->nnz, M, h->feat) / kStrippedRate;
+    if (f.hub_thr == 0 && !h->split_long && h->n_strips > 1 && h->n_long > 0 && (double)h->max_row_nnz * 100e-9 <= 0.5 * step_s) return Rebuild::kFoldHubs;
+    // Local columns, a wide B, segments that hold a quarter of the nonzeros and NO strips for them (columns out of order, or B beyond the rule): what is left
+    // to them is the length-sorted table that scatters neighbours -- the rows kernel takes them instead, up to 1 024 nonzeros (protein-unsorted N = 128 / 256:
+    // 0.83 - 0.85 of the time; profiles/r05_regret.md).  One more plan: ~0.3 ms of preprocess.
+    // (narrow B: up to 512 -- protein-unsorted kLen 32: 0.85 -- and only on graphs whose ROWS are long, mean degree >= 64: citation-community, mean 10, lost 17 % with it)
+    if (f.medium_thr == 0 && !h->split_long && h->local_pct >= 50 && h->local_pct < 95 && M >= 65536 && h->n_strips <= 1 && h->medium_res < keep_rows_to(h) &&
+        h->seg_nnz * 4 >= h->nnz && (h->feat >= 128 || h->nnz / M >= 64))
+        return Rebuild::kKeepRows;
+    return Rebuild::kKeep;
+}
+
+// The plan half of preprocess (mi_spmm_preprocess adds the tuner).  One sequence for both plan builders: hub threshold, column check, block detection,
+// the tables (device or host builder) and their strips, the post-build decision (at most one rebuild, plus the unfold fallback), partial sums, block
+// items, side streams.  The column check only launches here; the builder reads its flag back and rejects the CSR before any table is used (block
+// detection runs on an unvalidated row_ptr: detect_row_blocks keeps its own reads inside [0, nnz)).
+static int preprocess_plan(mi_spmm_handle *h)
+{
+    if (!good(h)) return MI_SPMM_ESTATE;
+    const auto t0 = std::chrono::steady_clock::now();
+    free_plan(h);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MI_SPMM_ENODEVICE;
     const int32_t M = h->num_v;
     auto tp = t0;
     auto lap = [&](int i) {
@@ -528,99 +720,47 @@ static int preprocess_on_gpu(mi_spmm_handle *h, std::chrono::steady_clock::time_
         h->phase_us[i] = std::chrono::duration<double, std::micro>(now - tp).count();
         tp = now;
     };
+    const int64_t thr = hub_threshold_for(h, h->in_force.hub_thr);
+    h->long_thr = thr;
+    if (!h->d_col_bad) HIP_TRY(hipMalloc((void **)&h->d_col_bad, 256));     // column-range flag; the 192 bytes behind it: column sample, strip survey
     lap(0);
-    unsigned int *d_bad = nullptr;
+    // column range: one pass over col_idx on the device (an out-of-range column is an out-of-bounds read of B, i.e. a GPU fault)
     if (h->nnz > 0) {
-        if (!h->d_col_bad) HIP_TRY(hipMalloc((void **)&h->d_col_bad, 256));
-        d_bad = h->d_col_bad;
-        hipError_t e = hipMemsetAsync(d_bad, 0, sizeof(unsigned int), 0);
+        hipError_t e = hipMemsetAsync(h->d_col_bad, 0, sizeof(unsigned int), 0);
         if (e == hipSuccess) {
             const int64_t want = (h->nnz + kBlockThreads * 8 - 1) / (kBlockThreads * 8);
             const int grid = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
-            hipLaunchKernelGGL(csr_check_cols, dim3(grid), dim3(kBlockThreads), 0, 0, h->d_idx, h->nnz, h->num_cols, d_bad);
+            hipLaunchKernelGGL(csr_check_cols, dim3(grid), dim3(kBlockThreads), 0, 0, h->d_idx, h->nnz, h->num_cols, h->d_col_bad);
             e = hipGetLastError();
         }
         if (e != hipSuccess) return (int)e;
     }
     lap(1);
+    // block path: 16-row groups with one shared column list (min_len <= L <= detection cap).  A group's list may be as long as the longest exact segment
+    // (auto hub threshold: at most its largest candidate).
     if (h->block_path && !h->ftz && block_path_shape_ok(h->feat) && M >= 16 && h->nnz > 0) {
         const int32_t n_groups = (M + 15) / 16;
         if (hipMalloc((void **)&h->d_blk_flag, (size_t)n_groups) != hipSuccess) return MI_SPMM_ENOMEM;
-        // a group's shared list may be as long as the longest exact segment (auto hub threshold: at most its largest candidate)
         hipLaunchKernelGGL(detect_row_blocks, dim3((n_groups + 3) / 4), dim3(kBlockThreads), 0, 0, h->d_ptr, h->d_idx, M, (int32_t)h->nnz,
-                           (int32_t)h->block_min_len, (int32_t)(h->long_thr > 0 ? h->long_thr : hist_threshold(kHistN - 1)), h->d_blk_flag);
+                           (int32_t)h->block_min_len, (int32_t)(thr > 0 ? thr : hist_threshold(kHistN - 1)), h->d_blk_flag);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { free_plan(h); return (int)e; }
     }
     lap(2);
-    // The plan, then the column strips of its segments -- and, where strips are in force and the hub threshold was ours to choose, a second plan WITHOUT
-    // hubs when the longest row's sub-chains would hide inside the strips' launches: as stripped segments those rows gather out of L2 like the rest,
-    // where the hub kernel gathers them out of all of B beside the strip launches (reddit-shaped N = 128 / 256: 5.07 -> 4.46, 8.97 -> 8.15 ms).  The longest
-    // row's chain, at 100 ns per nonzero over all strips, has to fit into half of the stripped step's estimate: at N = 32 the same graph's 20 758-nonzero row
-    // would be the step (1.08 -> 1.70 ms) and protein-shaped N = 32 loses 7 % (0.72 -> 0.78): both keep their hubs.  profiles/r04_col_strips.txt section 8
-    // (attempt 2, ADVICE r4: the folded plan surveys the former hub rows for the first time; if one of them has non-ascending columns, or the rule on
-    //  the new survey says no strips, the fold has nothing to stand on -- a 10^4-nonzero row would run as ONE unstripped segment chain -- and the plan
-    //  with hubs is built again, this time to be kept)
-    int32_t mthr_retry = 0;
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        PlanOut po;
-        const int64_t mthr_want = mthr_retry > 0 ? mthr_retry : h->medium_thr;
-        const int32_t mthr = (int32_t)((h->long_thr == 0 || mthr_want < h->long_thr) ? mthr_want : h->long_thr);   // 0 = auto
-        const int rc = build_plan_gpu(h->d_ptr, h->d_idx, M, h->num_cols, h->feat, h->nnz, h->d_blk_flag, d_bad, mthr, (int32_t)h->long_thr,
-                                      (int32_t)h->long_chunk, (int32_t)h->split_long, (int32_t)h->seg_order, &h->scratch_a, &h->scratch_b, &po);
-        h->d_chunks = po.d_chunks;
-        h->d_long = po.d_long;
-        h->d_blk_groups = po.d_blk_groups;
-        if (rc != 0) { free_plan(h); return rc; }
-        h->n_chunks = po.n_chunks;
-        h->n_long = po.n_long;
-        h->n_slots = po.n_slots;
-        h->n_medium = po.n_medium;
-        h->n_blk_groups = po.n_blk_groups;
-        h->max_row_nnz = po.max_len;
-        h->medium_res = po.mthr;
-        h->long_thr = po.thr;
-        h->local_pct = po.local_pct;
-        h->front_pct = po.front_pct;
-        h->seg_nnz = po.seg_nnz;
-        {
-            const int crc = plan_col_strips(h);
-            if (crc != 0) { free_plan(h); return crc; }
+    int rc = build_tables(h, thr, h->in_force.medium_thr);
+    const Rebuild next = rc == 0 ? next_plan(h, false) : Rebuild::kKeep;
+    if (next == Rebuild::kFoldHubs) {
+        drop_tables(h);
+        rc = build_tables(h, hub_threshold_for(h, 1 << 30), h->in_force.medium_thr);     // every row up to any length: one exact segment (stripped)
+        if (rc == 0 && next_plan(h, true) == Rebuild::kUnfold) {
+            drop_tables(h);
+            rc = build_tables(h, thr, h->in_force.medium_thr);
         }
-        const double step_s = ((double)h->nnz * (4.0 * h->feat + 8.0) + 4.0 * (double)M * h->feat) / 12e12;     // a stripped step: about twice the gather model's rate
-        const bool fold_hubs = attempt == 0 && h->long_thr_user == 0 && !h->split_long && h->n_strips > 1 && h->n_long > 0 &&
-                               (double)h->max_row_nnz * 100e-9 <= 0.5 * step_s;
-        const bool unfold = attempt == 1 && h->n_strips <= 1;      // the fold lost its strips: back to the plan with hubs
-        // Local columns, a wide B, segments that hold a quarter of the nonzeros and NO strips for them (columns out of order, or B beyond the rule): what is left
-        // to them is the length-sorted table that scatters neighbours -- the rows kernel takes them instead, up to 1 024 nonzeros (protein-unsorted N = 128 / 256:
-        // 0.83 - 0.85 of the time; profiles/r05_regret.md).  One more plan, on the device: ~0.3 ms of preprocess.
-        // (narrow B: up to 512 -- protein-unsorted kLen 32: 0.85)
-        //  and only on graphs whose ROWS are long, mean degree >= 64: citation-community, mean 10, lost 17 % with it)
-        const int32_t keep_to = h->feat >= 128 ? 1024 : 512;
-        const bool keep_rows = attempt == 0 && !fold_hubs && mthr_retry == 0 && h->medium_thr == 0 && !h->split_long && h->local_pct >= 50 && h->local_pct < 95 &&
-                               M >= 65536 && h->n_strips <= 1 && h->medium_res < keep_to && h->seg_nnz * 4 >= h->nnz && (h->feat >= 128 || h->nnz / M >= 64);
-        if (keep_rows) {
-            mthr_retry = keep_to;
-            if (h->d_chunks) (void)hipFree(h->d_chunks);
-            if (h->d_long) (void)hipFree(h->d_long);
-            if (h->d_blk_groups) (void)hipFree(h->d_blk_groups);
-            h->d_chunks = nullptr; h->d_long = nullptr; h->d_blk_groups = nullptr;
-            h->ws_bytes = 0;
-            h->long_thr = h->long_thr_user;      // auto again (0) or the caller's
-            attempt = -1;                        // the loop's ++ makes it 0: the same first attempt, with the other medium threshold
-            continue;
-        }
-        if (!fold_hubs && !unfold) break;
-        if (h->d_chunks) (void)hipFree(h->d_chunks);
-        if (h->d_long) (void)hipFree(h->d_long);
-        if (h->d_blk_groups) (void)hipFree(h->d_blk_groups);
-        h->d_chunks = nullptr;
-        h->d_long = nullptr;
-        h->d_blk_groups = nullptr;
-        h->ws_bytes = 0;
-        if (fold_hubs) h->long_thr = 1 << 30;          // every row up to any length: one exact segment (stripped)
-        else h->long_thr = 0;                           // auto threshold again: the first attempt's plan, kept this time
+    } else if (next == Rebuild::kKeepRows) {
+        drop_tables(h);
+        rc = build_tables(h, thr, keep_rows_to(h));
     }
+    if (rc != 0) { free_plan(h); return rc; }
     if (h->n_blk_groups == 0 && h->d_blk_flag) { (void)hipFree(h->d_blk_flag); h->d_blk_flag = nullptr; }
     h->n_rows_for_rows_kernel = (int64_t)M - 16 * (int64_t)h->n_blk_groups - (int64_t)h->n_long - (int64_t)h->n_medium;
     h->ldp = ((int64_t)h->feat + 3) / 4 * 4;
@@ -631,16 +771,11 @@ static int preprocess_on_gpu(mi_spmm_handle *h, std::chrono::steady_clock::time_
         h->ws_bytes += pb;
     }
     h->ws_bytes += (size_t)h->n_chunks * sizeof(Chunk) + (size_t)h->n_long * sizeof(LongRow);
-    {
-        const int brc = build_block_items(h);
-        if (brc != 0) { free_plan(h); return brc; }
-    }
+    rc = build_block_items(h);
     lap(4);
-    {
-        int src = ensure_side_streams(h);
-        if (src == 0) src = note_hub_rows(h);
-        if (src != 0) { free_plan(h); return src; }
-    }
+    if (rc == 0) rc = ensure_side_streams(h);
+    if (rc == 0) rc = note_hub_rows(h);
+    if (rc != 0) { free_plan(h); return rc; }
     // mi_spmm.h: preprocess synchronises.  Everything above ran on the null stream and most of it was waited for by the copies back, but the last
     // launches (build_col_strips, the block items' device copy) were not: a run() on a non-blocking stream is not ordered behind the null stream.
     HIP_TRY(hipStreamSynchronize(0));
@@ -697,9 +832,10 @@ int mi_spmm_create(mi_spmm_handle **out, const int32_t *d_row_ptr, const int32_t
     h->num_cols = num_cols;
     h->nnz = nnz;
     h->feat = feat_in;
-    h->medium_thr = 0;     // auto: 64, or 32 on skewed degree distributions (resolved in preprocess)
-    h->long_thr = 0;       // 0 = auto, resolved in preprocess: clamp(nnz / 8192, 256, 2048)
-    h->long_thr_user = 0;
+    // the tuner's seven: auto, resolved in preprocess and run (fused_step 2 = auto: run_part, short steps only)
+    h->user = Tunables{0, 0, 0, 0, 2, 0, 0};
+    h->in_force = h->user;
+    h->long_thr = 0;
     h->split_long = 0;     // every row one chain in stored order (the reference's definition, spmm_ref.cu:10-14)
     h->hub_slice = 0;
     h->hub_overlap = 1;
@@ -720,9 +856,7 @@ int mi_spmm_create(mi_spmm_handle **out, const int32_t *d_row_ptr, const int32_t
     h->gpu_preprocess = 1;
     h->block_threads = 256;
     h->split_cols = 1;
-    h->fused_step = 2;      // auto (run_part: short steps only)
     h->fused_order = 0;     // auto (run_part: the role whose longest chain lasts longest goes first)
-    h->col_strips = 0;      // auto (plan.hpp resolve_col_strips)
     h->n_strips = 1;
     h->seg_unsorted = -1;
     h->segment_unroll = 0;  // auto: 32 (the whole 32-pair item in flight: 0-13 % faster than 8 on every shape, profiles/r01_segment_unroll.txt) -- 16 for
@@ -766,8 +900,9 @@ int mi_spmm_set_option(mi_spmm_handle *h, const char *key, int64_t v)
     if (!good(h) || !key) return MI_SPMM_EINVAL;
     const std::string k(key);
     if (k == "use_graph") return MI_SPMM_EUNSUPPORTED;      // removed in round 5 (it only ever lost: profiles/r05_use_graph_experiment.md); a caller captures run() itself
-    else if (k == "medium_row_threshold") { if (v < 0) return MI_SPMM_EINVAL; h->medium_thr = v > INT32_MAX ? INT32_MAX : v; h->tuned_mask &= ~4u; free_plan(h); }
-    else if (k == "long_row_threshold") { if (v < 0) return MI_SPMM_EINVAL; h->long_thr_user = v > INT32_MAX ? INT32_MAX : v; h->long_thr = h->long_thr_user; h->tuned_mask &= ~64u; free_plan(h); }
+    // (the tuner's seven settings: set_option writes both copies, so that the keys that keep the plan take effect on the next run)
+    else if (k == "medium_row_threshold") { if (v < 0) return MI_SPMM_EINVAL; h->user.medium_thr = h->in_force.medium_thr = v > INT32_MAX ? INT32_MAX : v; free_plan(h); }
+    else if (k == "long_row_threshold") { if (v < 0) return MI_SPMM_EINVAL; h->user.hub_thr = h->in_force.hub_thr = h->long_thr = v > INT32_MAX ? INT32_MAX : v; free_plan(h); }
     else if (k == "split_long_rows") { h->split_long = v ? 1 : 0; free_plan(h); }
     else if (k == "hub_slice") { if (v != 0 && v != 16 && v != 32 && v != 64) return MI_SPMM_EINVAL; h->hub_slice = v; }
     else if (k == "hub_overlap") { if (v < 0 || v > 2) return MI_SPMM_EINVAL; h->hub_overlap = v; free_plan(h); }
@@ -795,14 +930,14 @@ int mi_spmm_set_option(mi_spmm_handle *h, const char *key, int64_t v)
     }
     else if (k == "gpu_preprocess") { h->gpu_preprocess = v ? 1 : 0; free_plan(h); }
     else if (k == "split_cols") h->split_cols = v ? 1 : 0;
-    else if (k == "tile_cols") { if (v != 0 && v != 32 && v != 64 && v != 128 && v != 256) return MI_SPMM_EINVAL; h->tile_cols = v; h->tuned_mask &= ~1u; }
+    else if (k == "tile_cols") { if (v != 0 && v != 32 && v != 64 && v != 128 && v != 256) return MI_SPMM_EINVAL; h->user.tile_cols = h->in_force.tile_cols = v; }
     else if (k == "segment_unroll") { if (v != 0 && v != 8 && v != 16 && v != 32) return MI_SPMM_EINVAL; h->segment_unroll = v; }
-    else if (k == "col_strips") { if (v < 0 || v > kMaxColStrips) return MI_SPMM_EINVAL; h->col_strips = v; h->tuned_mask &= ~2u; free_plan(h); }
-    else if (k == "fused_step") { if (v < 0 || v > 2) return MI_SPMM_EINVAL; h->fused_step = v; h->tuned_mask &= ~8u; }
+    else if (k == "col_strips") { if (v < 0 || v > kMaxColStrips) return MI_SPMM_EINVAL; h->user.col_strips = h->in_force.col_strips = v; free_plan(h); }
+    else if (k == "fused_step") { if (v < 0 || v > 2) return MI_SPMM_EINVAL; h->user.fused_step = h->in_force.fused_step = v; }
     else if (k == "fused_order") { if (v < 0 || v > 2) return MI_SPMM_EINVAL; h->fused_order = v; }
-    else if (k == "segment_order") { if (v < 0 || v > 2) return MI_SPMM_EINVAL; h->seg_order = v; h->tuned_mask &= ~16u; free_plan(h); }
+    else if (k == "segment_order") { if (v < 0 || v > 2) return MI_SPMM_EINVAL; h->user.seg_order = h->in_force.seg_order = v; free_plan(h); }
     else if (k == "autotune") { if (v != 0 && v != 1) return MI_SPMM_EINVAL; h->autotune = v; free_plan(h); }
-    else if (k == "rows_unroll") { if (v != 0 && v != 8 && v != 16) return MI_SPMM_EINVAL; h->rows_unroll = v; }
+    else if (k == "rows_unroll") { if (v != 0 && v != 8 && v != 16) return MI_SPMM_EINVAL; h->user.rows_unroll = h->in_force.rows_unroll = v; }
     else if (k == "col_strips_builder") { if (v != 0 && v != 1) return MI_SPMM_EINVAL; h->strips_builder = v; free_plan(h); }
     else if (k == "block_threads") { if (v != 64 && v != 128 && v != 256) return MI_SPMM_EINVAL; h->block_threads = v; }
     else if (k == "nt_store") h->nt_store = v ? 1 : 0;
@@ -822,7 +957,7 @@ int mi_spmm_get_option(const mi_spmm_handle *h, const char *key, int64_t *value)
     if (!good(h) || !key || !value) return MI_SPMM_EINVAL;
     const std::string k(key);
     if (k == "long_row_threshold") *value = h->long_thr;
-    else if (k == "medium_row_threshold") *value = h->prepared ? h->medium_res : h->medium_thr;
+    else if (k == "medium_row_threshold") *value = h->prepared ? h->medium_res : h->in_force.medium_thr;
     else if (k == "n_medium_rows") *value = h->n_medium;
     else if (k == "n_partial_slots") *value = h->n_slots;
     else if (k == "long_row_chunk") *value = h->long_chunk;
@@ -841,24 +976,24 @@ int mi_spmm_get_option(const mi_spmm_handle *h, const char *key, int64_t *value)
     else if (k == "block_threads") *value = h->block_threads;
     else if (k == "segment_unroll") *value = h->segment_unroll;
     else if (k == "split_cols") *value = h->split_cols;
-    else if (k == "tile_cols") *value = h->tile_cols;
+    else if (k == "tile_cols") *value = h->in_force.tile_cols;
     else if (k == "nt_store") *value = h->nt_store;
     else if (k == "nt_stream") *value = h->nt_stream;
     else if (k == "block_path") *value = h->block_path;
     else if (k == "n_long_rows") *value = h->n_long;
     else if (k == "n_chunks") *value = h->n_chunks;
-    else if (k == "col_strips") *value = h->col_strips;
+    else if (k == "col_strips") *value = h->in_force.col_strips;
     else if (k == "n_col_strips") *value = h->n_strips;
     else if (k == "segments_unsorted") *value = h->seg_unsorted;
     else if (k == "col_strips_builder") *value = h->strips_builder;
-    else if (k == "fused_step") *value = h->fused_step;
-    else if (k == "segment_order") *value = h->seg_order;
+    else if (k == "fused_step") *value = h->in_force.fused_step;
+    else if (k == "segment_order") *value = h->in_force.seg_order;
     else if (k == "autotune") *value = h->autotune;
-    else if (k == "rows_unroll") *value = h->rows_unroll;
+    else if (k == "rows_unroll") *value = h->in_force.rows_unroll;
     else if (k == "autotune_evals") *value = h->tune_evals;
     else if (k == "autotune_auto_us") *value = (int64_t)(h->tune_auto_ms * 1e3);
     else if (k == "autotune_best_us") *value = (int64_t)(h->tune_best_ms * 1e3);
-    else if (k == "autotune_mask") *value = h->tuned_mask;
+    else if (k == "autotune_mask") *value = tuned_settings(h->user, h->in_force);
     else if (k == "fused_step_in_force") *value = h->last_fused;
     else if (k == "fused_order") *value = h->fused_order;
     else if (k == "rows_unroll_in_force") *value = h->last_rows_deep ? 16 : 8;
@@ -904,235 +1039,6 @@ int mi_spmm_get_option(const mi_spmm_handle *h, const char *key, int64_t *value)
     else if (k == "pre_upload_us") *value = (int64_t)h->phase_us[4];
     else if (k == "prepared") *value = h->prepared ? 1 : 0;
     else return MI_SPMM_EUNSUPPORTED;
-    return MI_SPMM_OK;
-}
-
-// The plan half of preprocess (mi_spmm_preprocess, below run_rows, adds the optional graph capture).
-static int preprocess_plan(mi_spmm_handle *h)
-{
-    if (!good(h)) return MI_SPMM_ESTATE;
-    const auto t0 = std::chrono::steady_clock::now();
-    free_plan(h);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return MI_SPMM_ENODEVICE;
-
-    const int32_t M = h->num_v;
-    // Hub threshold.  Rows up to it stay ONE exact segment of the segment kernel; longer ones (hubs) go to the hub kernel
-    // (stored order) or, with "split_long_rows", are cut into pieces.  An explicit value is taken as is.  auto:
-    //   split mode: 2048 once there is enough work to hide a 2048-nonzero segment (nnz >= 2^24), proportionally lower for
-    //     small matrices (profiles/r01_thresholds.txt);
-    //   default (exact) mode: plan.hpp resolve_hub_threshold (needs the row-length histogram: resolved inside the plan builders).
-    if (h->long_thr_user > 0) h->long_thr = h->long_thr_user;
-    else if (h->split_long) {
-        int64_t t = h->nnz / 8192;
-        h->long_thr = t < 256 ? 256 : (t > 2048 ? 2048 : t);
-    } else h->long_thr = 0;     // resolved by the plan builder from the row-length histogram (plan.hpp: resolve_hub_threshold)
-    // The hub kernel moves 16-byte parts of B rows: a B narrower than one part keeps its long rows as single exact
-    // segments of the segment kernel (slow on a real hub, but N < 4 has no bandwidth to speak of either way).
-    if (!h->split_long && h->feat < 4) h->long_thr = INT32_MAX;
-    if (h->gpu_preprocess) return preprocess_on_gpu(h, t0);
-    std::vector<int32_t> ptr((size_t)M + 1);
-    HIP_TRY(hipMemcpy(ptr.data(), h->d_ptr, sizeof(int32_t) * ((size_t)M + 1), hipMemcpyDeviceToHost));
-    // data.cu:40-45 asserts ptr[num_v] == num_e; we also need monotone rows,
-    // or the kernels would read outside col_idx/vals.
-    if (ptr[0] < 0 || (int64_t)ptr[M] != h->nnz) return MI_SPMM_ECSR;
-    int32_t max_len = 0;
-    for (int32_t r = 0; r < M; ++r) {
-        const int32_t len = ptr[r + 1] - ptr[r];
-        if (len < 0) return MI_SPMM_ECSR;
-        if (len > max_len) max_len = len;
-    }
-    if (ptr[0] != 0 && (int64_t)ptr[0] > h->nnz) return MI_SPMM_ECSR;
-    h->max_row_nnz = max_len;
-    // (as in the device builder: a block group's list may be as long as the largest candidate of the auto threshold)
-    const int32_t detect_max = (int32_t)(h->long_thr > 0 ? h->long_thr : hist_threshold(kHistN - 1));
-    // the column sample the device builder takes inside its own pass (locality: tile width, medium threshold, strips; front-loaded columns: strips)
-    if (h->nnz > 0) {
-        if (!h->d_col_bad) HIP_TRY(hipMalloc((void **)&h->d_col_bad, 256));
-        const int src = sample_columns_gpu(h->d_ptr, h->d_idx, M, h->num_cols, h->nnz, (char *)h->d_col_bad + 64, &h->local_pct, &h->front_pct);
-        if (src != 0) return src;
-    } else h->local_pct = 0;
-    if (h->long_thr == 0) {      // auto, exact mode: the same histogram and the same rule as the device builder
-        LenHist hist;
-        std::memset(&hist, 0, sizeof(hist));
-        for (int32_t r = 0; r < M; ++r) {
-            const int32_t len = ptr[r + 1] - ptr[r];
-            for (int i = 0; i < kHistN && len > hist_threshold(i); ++i) { ++hist.cnt[i]; hist.nnz[i] += (unsigned long long)len; }
-        }
-        h->long_thr = resolve_hub_threshold(h->nnz, M, h->num_cols, h->feat, hist.nnz, max_len);
-    }
-    auto lap = [&](int i, std::chrono::steady_clock::time_point &from) {
-        const auto now = std::chrono::steady_clock::now();
-        h->phase_us[i] = std::chrono::duration<double, std::micro>(now - from).count();
-        from = now;
-    };
-    auto tp = t0;
-    lap(0, tp);
-
-    // column range: one pass over col_idx on the device (an out-of-range
-    // column is an out-of-bounds read of B, i.e. a GPU fault)
-    if (h->nnz > 0) {
-        unsigned int *d_bad = nullptr;
-        HIP_TRY(hipMalloc((void **)&d_bad, 256));
-        hipError_t e = hipMemset(d_bad, 0, sizeof(unsigned int));
-        if (e == hipSuccess) {
-            const int64_t want = (h->nnz + kBlockThreads * 8 - 1) / (kBlockThreads * 8);
-            const int grid = (int)(want < 1 ? 1 : (want > 4096 ? 4096 : want));
-            hipLaunchKernelGGL(csr_check_cols, dim3(grid), dim3(kBlockThreads), 0, 0, h->d_idx, h->nnz,
-                               h->num_cols, d_bad);
-            e = hipGetLastError();
-        }
-        unsigned int bad = 0;
-        if (e == hipSuccess) e = hipMemcpy(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost);
-        (void)hipFree(d_bad);
-        if (e != hipSuccess) return (int)e;
-        if (bad) return MI_SPMM_ECSR;
-    }
-
-    lap(1, tp);
-    // block path: 16-row groups with one shared column list (min_len <= L <= split threshold)
-    {
-        const int32_t N = h->feat;
-        const bool n_ok = block_path_shape_ok(N);
-        if (h->block_path && !h->ftz && n_ok && M >= 16 && h->nnz > 0) {
-            const int32_t n_groups = (M + 15) / 16;
-            if (hipMalloc((void **)&h->d_blk_flag, (size_t)n_groups) != hipSuccess) return MI_SPMM_ENOMEM;
-            const int grid = (n_groups + 3) / 4;  // one wave per group
-            hipLaunchKernelGGL(detect_row_blocks, dim3(grid), dim3(kBlockThreads), 0, 0, h->d_ptr, h->d_idx, M, (int32_t)h->nnz,
-                               (int32_t)h->block_min_len, detect_max, h->d_blk_flag);
-            hipError_t e = hipGetLastError();
-            std::vector<uint8_t> flags((size_t)n_groups);
-            if (e == hipSuccess) e = hipMemcpy(flags.data(), h->d_blk_flag, (size_t)n_groups, hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { free_plan(h); return (int)e; }
-            std::vector<int32_t> groups;
-            for (int32_t g = 0; g < n_groups; ++g) if (flags[(size_t)g]) groups.push_back(g);
-            if (groups.empty()) {
-                (void)hipFree(h->d_blk_flag);
-                h->d_blk_flag = nullptr;
-            } else {
-                if (hipMalloc((void **)&h->d_blk_groups, groups.size() * sizeof(int32_t)) != hipSuccess) { free_plan(h); return MI_SPMM_ENOMEM; }
-                e = hipMemcpy(h->d_blk_groups, groups.data(), groups.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-                if (e != hipSuccess) { free_plan(h); return (int)e; }
-                h->n_blk_groups = (int32_t)groups.size();
-            }
-        }
-    }
-
-    lap(2, tp);
-    // Segment table (the reference's Task list, spmm_opt.cu:43-54, kept only for rows that need it):
-    //   len > long_thr                 -> pieces of long_chunk nonzeros, partial sums + ordered reduce
-    //   medium_thr < len <= long_thr   -> ONE segment = the whole row, stored straight to C (exact order)
-    // Rows of block-path groups are excluded (their L <= long_thr by construction).  Segments are
-    // sorted longest first: neighbours in a wave have similar lengths and the tail is short.
-    std::vector<uint8_t> flags_host;
-    if (h->n_blk_groups > 0) {
-        flags_host.resize((size_t)(M + 15) / 16);
-        HIP_TRY(hipMemcpy(flags_host.data(), h->d_blk_flag, flags_host.size(), hipMemcpyDeviceToHost));
-    }
-    std::vector<Chunk> chunks;
-    std::vector<LongRow> longs;
-    const int32_t thr = (int32_t)h->long_thr, clen = (int32_t)h->long_chunk;
-    // the same auto rule as the device builder (plan.hpp resolve_medium_threshold)
-    const int32_t mthr = resolve_medium_threshold((int32_t)h->medium_thr, h->nnz, M, max_len,
-                                                  (int32_t)(h->long_thr > INT32_MAX ? INT32_MAX : h->long_thr), h->local_pct, h->feat);
-    h->medium_res = mthr;
-    int32_t n_slots = 0, n_medium = 0;
-    if (max_len > mthr) {
-        chunks.reserve(1 << 16);
-        for (int32_t r = 0; r < M; ++r) {
-            const int32_t beg = ptr[r], end = ptr[r + 1], len = end - beg;
-            if (len <= mthr) continue;
-            if (!flags_host.empty() && flags_host[(size_t)(r >> 4)]) continue;      // block path owns it, whatever its length
-            if (len <= thr) {
-                Chunk c;
-                c.beg = beg;
-                c.end = end;
-                c.slot = -1;
-                c.row = r;
-                chunks.push_back(c);
-                ++n_medium;
-                continue;
-            }
-            LongRow L;
-            L.row = r;
-            L.len = len;
-            if (!h->split_long) {      // exact order: the hub kernel walks the row whole
-                L.first_slot = -1;
-                L.n_chunks = 0;
-                longs.push_back(L);
-                continue;
-            }
-            L.first_slot = n_slots;
-            L.n_chunks = 0;
-            for (int32_t b = beg; b < end; b += (end - b > clen ? clen : end - b)) {
-                Chunk c;
-                c.beg = b;
-                c.end = (end - b > clen) ? b + clen : end;
-                c.slot = n_slots++;
-                c.row = r;
-                chunks.push_back(c);
-                ++L.n_chunks;
-            }
-            longs.push_back(L);
-        }
-        // hub rows longest first, ties in row order (as the device builder's stable radix sort leaves them)
-        std::stable_sort(longs.begin(), longs.end(), [](const LongRow &x, const LongRow &y) { return x.len > y.len; });
-        // longest first, stable: counting sort on the length (<= max(long_thr, long_chunk) by construction) -- unless the row order was asked for
-        if (h->seg_order != 2) {
-        int32_t lmax = 0;
-        for (const Chunk &c : chunks) lmax = std::max(lmax, c.end - c.beg);
-        std::vector<int32_t> start((size_t)lmax + 2, 0);
-        for (const Chunk &c : chunks) ++start[(size_t)(lmax - (c.end - c.beg)) + 1];
-        for (size_t i = 1; i < start.size(); ++i) start[i] += start[i - 1];
-        std::vector<Chunk> sorted(chunks.size());
-        for (const Chunk &c : chunks) sorted[(size_t)start[(size_t)(lmax - (c.end - c.beg))]++] = c;
-        chunks.swap(sorted);
-        }
-    }
-    h->n_chunks = (int32_t)chunks.size();
-    h->n_long = (int32_t)longs.size();
-    h->seg_nnz = 0;
-    for (const Chunk &c : chunks) if (c.slot < 0) h->seg_nnz += c.end - c.beg;
-    h->n_medium = n_medium;
-    h->n_slots = n_slots;
-    h->n_rows_for_rows_kernel = (int64_t)M - 16 * (int64_t)h->n_blk_groups - (int64_t)h->n_long - (int64_t)n_medium;
-    h->ldp = ((int64_t)h->feat + 3) / 4 * 4;
-    lap(3, tp);
-    if (h->n_chunks > 0 || h->n_long > 0) {
-        const size_t cb = chunks.size() * sizeof(Chunk), lb = longs.size() * sizeof(LongRow);
-        const size_t pb = (size_t)n_slots * (size_t)h->ldp * sizeof(float);
-        if (hipMalloc((void **)&h->d_chunks, cb ? cb : 16) != hipSuccess ||
-            hipMalloc((void **)&h->d_long, lb ? lb : 16) != hipSuccess ||
-            (pb && hipMalloc((void **)&h->d_partials, pb) != hipSuccess)) {
-            free_plan(h);
-            return MI_SPMM_ENOMEM;
-        }
-        hipError_t e = cb ? hipMemcpy(h->d_chunks, chunks.data(), cb, hipMemcpyHostToDevice) : hipSuccess;
-        if (e == hipSuccess && lb) e = hipMemcpy(h->d_long, longs.data(), lb, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            free_plan(h);
-            return (int)e;
-        }
-        h->ws_bytes = cb + lb + pb;
-    }
-    {
-        const int brc = build_block_items(h);
-        if (brc != 0) { free_plan(h); return brc; }
-    }
-    {
-        const int crc = plan_col_strips(h);
-        if (crc != 0) { free_plan(h); return crc; }
-    }
-    lap(4, tp);
-    {
-        int src = ensure_side_streams(h);
-        if (src == 0) src = note_hub_rows(h);
-        if (src != 0) { free_plan(h); return src; }
-    }
-    HIP_TRY(hipStreamSynchronize(0));      // (as in preprocess_on_gpu: build_col_strips is asynchronous)
-    h->prepared = true;
-    h->preprocess_us =
-        std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     return MI_SPMM_OK;
 }
 
@@ -1275,7 +1181,7 @@ void launch_hub(int sw, bool excl, const HubArgs &a, dim3 grid, hipStream_t s)
 int resolve_tile_cols(const mi_spmm_handle *h, int32_t N, int64_t ldb)
 {
     (void)ldb;
-    if (h->tile_cols > 0) return (int)h->tile_cols;
+    if (h->in_force.tile_cols > 0) return (int)h->in_force.tile_cols;
     if (h->local_pct < 0 || h->local_pct >= 95) return 256;
     if (h->local_pct >= 50) {
         if (N < 256) return 256;
@@ -1284,7 +1190,7 @@ int resolve_tile_cols(const mi_spmm_handle *h, int32_t N, int64_t ldb)
         return (mean_l < 8 && 4.0 * (double)h->num_cols * (double)N > 256.0 * 1048576.0) ? 256 : 128;
     }
     // an L2-resident B (4 K N <= 6 MiB: ddi-shaped) has no working set to shrink: narrower tiles only re-read A (ddi-community N = 256: 0.76 with the whole wave)
-    if (4.0 * (double)h->num_cols * (double)N <= 6.0 * 1048576.0) return 256;
+    if (b_l2_resident(h->num_cols, N)) return 256;
     const int64_t mean = h->num_v > 0 ? h->nnz / h->num_v : 0;
     const bool hubs = (int64_t)h->max_row_nnz > 64 * (mean > 1 ? mean : 1);
     // (... except two tiles of 64 at N = 128 when the hubs come first in the vertex order: their B rows are the hot set, and half-width rows of it fit L2 --
@@ -1366,21 +1272,22 @@ static int run_part(mi_spmm_handle *h, const float *d_vin, int64_t ldb, float *d
     // default workgroup size.  auto ("fused_step" = 2): only steps whose bytes take under 0.2 ms at 6 TB/s -- there the launch boundaries and the fork are
     // a third of the step and the rows role's lower occupancy (3 waves per SIMD, the hub role's footprint) costs nothing; longer steps keep their kernels.
     {
-        const double step_bytes = (double)h->nnz * (4.0 * full.N + 8.0) + 4.0 * (double)h->num_v * full.N;
         const bool eligible = vec4 && !wide && col_tiles == 1 && launch_blocks_here && N == full.N && h->n_strips <= 1 && !h->split_long && h->n_blk_groups == 0 &&
                               bt == kBlockThreads && pol == kPolNtStore && (h->n_long > 0 || h->n_chunks > 0) &&
                               (int64_t)((full.N + 15) / 16) * h->n_long + (int64_t)h->n_chunks + nblk64 < (int64_t)INT32_MAX;
         // auto: the step's bytes take under 0.1 ms, or its longest row's chain (3.2 ns per nonzero) outlasts them anyway (am-shaped): then the rows role's
         // occupancy cannot matter.  (First rule, 0.2 ms: youtube-shaped kLen 32 -- 0.155 ms of bytes, a 75 us chain, 35 K rows workgroups -- lost 6 - 14 %.)
         // (an L2-resident B -- 4 K N <= 6 MiB, ddi-shaped -- moves its bytes three times faster: priced as in plan.hpp resolve_hub_threshold)
-        const double t_bytes = step_bytes / (4.0 * (double)h->num_cols * (double)full.N <= 6.0 * 1048576.0 ? 18e12 : 6e12);
+        constexpr double kFabricRate = 6e12, kL2Rate = 18e12;
+        const double t_bytes = gather_bytes(h->nnz, h->num_v, full.N) / (b_l2_resident(h->num_cols, full.N) ? kL2Rate : kFabricRate);
         // (local columns: the rows kernel alone is fast and wants its occupancy -- 0.1 ms; columns anywhere: latency-bound whatever the occupancy -- 0.16 ms:
         //  arxiv-community N = 128 loses 18 % fused, arxiv-rcm gains 16 %; youtube-community kLen 32 loses 14 %, youtube-shuffled gains 11 %)
         const double t_fused = h->local_pct >= 50 ? 100e-6 : 160e-6;
         // (a step that is ONE launch anyway -- one role only: ddi-shaped N = 256, every row a segment -- keeps that role's own kernel, which is the better
         //  instance of it: segments 32 gathers deep instead of 16 at the small-step kernel's footprint; ddi-community kLen 256: 85.7 -> 79 us)
         const int n_roles = ((h->n_long > 0 && range_has_hub(h, row_begin, row_end)) ? 1 : 0) + (h->n_chunks > 0 ? 1 : 0) + (h->n_rows_for_rows_kernel > 0 ? 1 : 0);
-        const bool want = h->fused_step == 1 || (h->fused_step == 2 && n_roles >= 2 && (t_bytes < t_fused || (double)h->max_row_nnz * 3.2e-9 > t_bytes));
+        const int64_t fused_step = h->in_force.fused_step;
+        const bool want = fused_step == 1 || (fused_step == 2 && n_roles >= 2 && (t_bytes < t_fused || (double)h->max_row_nnz * 3.2e-9 > t_bytes));
         h->last_fused = 0;
         if (eligible && want) {
             SmallStepArgs fa{};
@@ -1408,7 +1315,7 @@ static int run_part(mi_spmm_handle *h, const float *d_vin, int64_t ldb, float *d
             // nonzeros is the step -> hubs first; ddi- / collab-shaped: hub rows of 700 - 1 800 nonzeros (2 - 6 us) over 256 - 512-nonzero segments
             // (12 - 24 us) that used to START behind two rounds of hub workgroups -> segments first.
             {
-                const bool l2_b = 4.0 * (double)h->num_cols * (double)full.N <= 6.0 * 1048576.0;
+                const bool l2_b = b_l2_resident(h->num_cols, full.N);
                 const int64_t seg_max = h->long_thr > 0 && h->long_thr < (int64_t)h->max_row_nnz ? h->long_thr : (int64_t)h->max_row_nnz;
                 const double t_seg = (double)seg_max * (l2_b ? 30e-9 : 47e-9), t_hub = 2e-6 + (double)h->max_row_nnz * 3.2e-9;
                 const bool both = fa.hub_wgs > 0 && fa.seg_wgs > 0;
@@ -1428,6 +1335,8 @@ static int run_part(mi_spmm_handle *h, const float *d_vin, int64_t ldb, float *d
     // The hub kernel goes first (its longest row is the step's longest dependent chain) and, like the block kernel,
     // addresses the full width: it is launched with the first column part only.
     if (h->n_long > 0 && !h->split_long && launch_blocks_here && range_has_hub(h, row_begin, row_end)) {
+        // the hub kernel moves 16-byte parts of B rows: its last part starts at column N - 4 (hub_threshold_for gives a narrower B no hubs)
+        if (full.N < 4) return MI_SPMM_EUNSUPPORTED;
         HubArgs ha{};
         ha.rows = h->d_long;
         ha.row_ptr = h->d_ptr;
@@ -1451,7 +1360,8 @@ static int run_part(mi_spmm_handle *h, const float *d_vin, int64_t ldb, float *d
         int sw = (int)h->hub_slice;
         bool excl = false;         // the chain-bound case: the hub workgroups keep their CUs to themselves (spmm_kernels.hpp EXCL)
         if (sw <= 0) {
-            const double step_s = ((double)h->nnz * (4.0 * full.N + 8.0) + 4.0 * (double)h->num_v * full.N) / 6e12;
+            constexpr double kFabricRate = 6e12;
+            const double step_s = gather_bytes(h->nnz, h->num_v, full.N) / kFabricRate;
             // (round 4, new chain loop: 16 and 32 are within 1-3 % of each other on chain-bound graphs up to N = 128; at N = 256 the 16 workgroups
             //  of a row cost more than they save: am-shaped 1.164 -> 1.119 ms with 32; 64 loses everywhere it is the chain that counts)
             const bool chain_bound = full.N <= 128 && (double)h->max_row_nnz * 3.3e-9 > 0.5 * step_s;
@@ -1581,7 +1491,8 @@ static int run_part(mi_spmm_handle *h, const float *d_vin, int64_t ldb, float *d
     // rows of hundreds of nonzeros here: medium threshold 1 024), ONE whole-wave column tile (N = 193 ... 256: at N = 512 the second tile's wave shares the
     // row's B rows and 16 gains nothing) and a mean degree >= 256.  Then a row is one wave's chain of round trips and 16 halves them: banded 300-700 rows
     // 0.89 (band +-2048) / 0.90 (+-512), 600-1000 rows 0.93; mean degree 150 and below: 0.98 ... 1.06 (profiles/r05_banded_unroll_ab.jsonl)
-    const bool deep_rows = h->rows_unroll == 16 || (h->rows_unroll == 0 && h->local_pct >= 95 && lpr == 64 && col_tiles == 1 && h->medium_res >= 512 &&
+    const int64_t rows_unroll = h->in_force.rows_unroll;
+    const bool deep_rows = rows_unroll == 16 || (rows_unroll == 0 && h->local_pct >= 95 && lpr == 64 && col_tiles == 1 && h->medium_res >= 512 &&
                                                     M > 0 && h->nnz / M >= 256);
     h->last_rows_deep = deep_rows && vec4 && !wide && bt == kBlockThreads && pol == kPolNtStore ? 1 : 0;
     // every row may already be owned by the segment, split and block paths: nothing left to launch
@@ -1699,7 +1610,8 @@ static int time_step(mi_spmm_handle *h, const float *d_vin, float *d_vout, hipEv
 {
     PeerOut po;
     std::memset(&po, 0, sizeof(po));
-    const double est_ms = ((double)h->nnz * (4.0 * h->feat + 8.0) + 4.0 * (double)h->num_v * h->feat) / 8e9;
+    constexpr double kBytesPerMs = 8e9;      // 8 TB/s
+    const double est_ms = gather_bytes(h->nnz, h->num_v, h->feat) / kBytesPerMs;
     int reps = (int)(1.0 / (est_ms > 0.01 ? est_ms : 0.01)) + 1;
     reps = reps < 3 ? 3 : (reps > 20 ? 20 : reps);
     double best = 1e30;
@@ -1724,12 +1636,11 @@ static int autotune_plan(mi_spmm_handle *h, const float *d_vin, float *d_vout)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     HIP_TRY(hipEventCreate(&e0));
     if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return MI_SPMM_ENOMEM; }
-    struct Cfg { int64_t tile, strips, mthr, fused, order, unroll, thr; };
-    auto apply = [&](const Cfg &c) { h->tile_cols = c.tile; h->col_strips = c.strips; h->medium_thr = c.mthr; h->fused_step = c.fused; h->seg_order = c.order; h->rows_unroll = c.unroll; h->long_thr_user = c.thr; };
-    // what the caller left to us (an explicit value of the caller's is never touched); the plan of these settings is the one in force
-    const bool own_tile = h->tile_cols == 0, own_strips = h->col_strips == 0, own_mthr = h->medium_thr == 0, own_fused = h->fused_step == 2, own_order = h->seg_order == 0;
-    const bool own_unroll = h->rows_unroll == 0, own_thr = h->long_thr_user == 0 && !h->split_long && h->feat >= 4;
-    Cfg best = {h->tile_cols, h->col_strips, h->medium_thr, h->fused_step, h->seg_order, h->rows_unroll, h->long_thr_user};
+    // what the caller left to us (an explicit value of the caller's is never touched); candidates go to in_force, user stays the caller's
+    const Tunables &u = h->user;
+    const bool own_tile = u.tile_cols == 0, own_strips = u.col_strips == 0, own_mthr = u.medium_thr == 0, own_fused = u.fused_step == 2, own_order = u.seg_order == 0;
+    const bool own_unroll = u.rows_unroll == 0, own_thr = u.hub_thr == 0 && !h->split_long && h->feat >= 4;
+    Tunables best = h->in_force;        // (= user: the plan in force is the auto plan)
     double best_ms = 0.0;
     int rc = time_step(h, d_vin, d_vout, e0, e1, &best_ms);
     h->tune_auto_ms = best_ms;
@@ -1737,9 +1648,9 @@ static int autotune_plan(mi_spmm_handle *h, const float *d_vin, float *d_vout)
     const int32_t N = h->feat, S_auto = h->n_strips, tile_auto = h->last_lpr * 4, mthr_auto = (int32_t)h->medium_res;
     const bool fused_auto = h->last_fused != 0, rows_deep_auto = h->last_rows_deep != 0;
     const int64_t thr_auto = h->long_thr;        // the resolved hub threshold of the auto plan (1 << 30: the hub fold; 8192 with no row above it: no hubs)
-    auto consider = [&](Cfg c) {
+    auto consider = [&](const Tunables &c) {
         if (rc != MI_SPMM_OK) return;
-        apply(c);
+        h->in_force = c;
         rc = preprocess_plan(h);
         double ms = 0.0;
         if (rc == MI_SPMM_OK) rc = time_step(h, d_vin, d_vout, e0, e1, &ms);
@@ -1751,24 +1662,22 @@ static int autotune_plan(mi_spmm_handle *h, const float *d_vin, float *d_vout)
     // the hub threshold one notch down and one up (a power-of-two ladder, 256 ... 8192): half of auto is 5 - 10 % faster on yelp- / youtube-shaped graphs and an
     // R-MAT of scale 18, 4 - 15 % slower on ddi- / protein-shaped ones and an R-MAT of scale 20 -- no plan statistic separates them (profiles/r05_regret*.md)
     if (own_thr && thr_auto >= 256 && thr_auto <= 8192 && h->max_row_nnz > 256)
-        for (int64_t t : {thr_auto / 2, thr_auto * 2}) if (t >= 256 && t <= 8192 && (t < thr_auto || h->max_row_nnz > thr_auto)) { Cfg c = best; c.thr = t; consider(c); }
-    if (own_mthr) for (int64_t m : {32, 64, 256, 1024}) if (m != mthr_auto) { Cfg c = best; c.mthr = m; consider(c); }
+        for (int64_t t : {thr_auto / 2, thr_auto * 2}) if (t >= 256 && t <= 8192 && (t < thr_auto || h->max_row_nnz > thr_auto)) { Tunables c = best; c.hub_thr = t; consider(c); }
+    if (own_mthr) for (int64_t m : {32, 64, 256, 1024}) if (m != mthr_auto) { Tunables c = best; c.medium_thr = m; consider(c); }
     if (own_strips) {
         const int64_t cand[3] = {1, S_auto > 1 ? (S_auto / 2 > 1 ? S_auto / 2 : 2) : 4, S_auto > 1 ? (2 * S_auto < kMaxColStrips ? 2 * S_auto : kMaxColStrips) : 12};
-        for (int64_t sc : cand) if (sc != S_auto) { Cfg c = best; c.strips = sc; consider(c); }
+        for (int64_t sc : cand) if (sc != S_auto) { Tunables c = best; c.col_strips = sc; consider(c); }
     }
-    if (own_tile && N > 64) for (int64_t t : {64, 128, 256}) if (t != tile_auto && (t < N || t == 256) && !(t == 256 && tile_auto >= N)) { Cfg c = best; c.tile = t; consider(c); }
-    if (own_fused) { Cfg c = best; c.fused = fused_auto ? 0 : 1; consider(c); }
-    if (own_order && h->n_chunks > 0) { Cfg c = best; c.order = 2; consider(c); }        // segments as the rows come (auto: by length)
+    if (own_tile && N > 64) for (int64_t t : {64, 128, 256}) if (t != tile_auto && (t < N || t == 256) && !(t == 256 && tile_auto >= N)) { Tunables c = best; c.tile_cols = t; consider(c); }
+    if (own_fused) { Tunables c = best; c.fused_step = fused_auto ? 0 : 1; consider(c); }
+    if (own_order && h->n_chunks > 0) { Tunables c = best; c.seg_order = 2; consider(c); }        // segments as the rows come (auto: by length)
     // 16 gathers in flight per lane group of the rows kernel (auto: 8): -13 % on banded 300-700 rows at N = 256, -8 % on rows of 4 - 12 at N = 128 / 256,
     // -1 % on C1 / C2, +4 ... +23 % on community-ordered graphs (occupancy): no rule of the plan's statistics separates them (profiles/r05_rows_unroll_ab.txt)
-    if (own_unroll && !fused_auto) { Cfg c = best; c.unroll = rows_deep_auto ? 8 : 16; consider(c); }      // (the other depth than the rule's)
+    if (own_unroll && !fused_auto) { Tunables c = best; c.rows_unroll = rows_deep_auto ? 8 : 16; consider(c); }      // (the other depth than the rule's)
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (rc != MI_SPMM_OK) { apply({own_tile ? 0 : h->tile_cols, own_strips ? 0 : h->col_strips, own_mthr ? 0 : h->medium_thr, own_fused ? 2 : h->fused_step, own_order ? 0 : h->seg_order, own_unroll ? 0 : h->rows_unroll, own_thr ? 0 : h->long_thr_user}); return rc; }
-    apply(best);
-    h->tuned_mask = (own_tile && best.tile != 0 ? 1u : 0u) | (own_strips && best.strips != 0 ? 2u : 0u) | (own_mthr && best.mthr != 0 ? 4u : 0u) |
-                    (own_fused && best.fused != 2 ? 8u : 0u) | (own_order && best.order != 0 ? 16u : 0u) | (own_unroll && best.unroll != 0 ? 32u : 0u) | (own_thr && best.thr != 0 ? 64u : 0u);
+    if (rc != MI_SPMM_OK) { h->in_force = h->user; return rc; }
+    h->in_force = best;
     h->tune_best_ms = best_ms;
     return preprocess_plan(h);              // the winner's plan (also when the winner is the auto plan: the last candidate's tables are in place otherwise)
 }
@@ -1776,16 +1685,7 @@ static int autotune_plan(mi_spmm_handle *h, const float *d_vin, float *d_vout)
 int mi_spmm_preprocess(mi_spmm_handle *h, const float *d_vin, float *d_vout)
 {
     // the reference zeroes vout here (spmm_opt.cu:67-68) because its kernel accumulates; ours overwrites, so vout is left alone -- unless "autotune" is on
-    if (good(h) && h->tuned_mask) {         // what an earlier tuning set goes back to auto: tuned again below, or simply auto when the option is off now
-        if (h->tuned_mask & 1u) h->tile_cols = 0;
-        if (h->tuned_mask & 2u) h->col_strips = 0;
-        if (h->tuned_mask & 4u) h->medium_thr = 0;
-        if (h->tuned_mask & 8u) h->fused_step = 2;
-        if (h->tuned_mask & 16u) h->seg_order = 0;
-        if (h->tuned_mask & 32u) h->rows_unroll = 0;
-        if (h->tuned_mask & 64u) h->long_thr_user = 0;
-        h->tuned_mask = 0;
-    }
+    if (good(h)) h->in_force = h->user;     // what an earlier tuning chose goes back to the caller's settings: tuned again below, or simply auto
     const int rc = preprocess_plan(h);
     if (rc != MI_SPMM_OK) return rc;
     if (h->autotune && d_vin && d_vout && h->num_v > 0 && h->feat >= 4 && h->nnz > 0 && !h->split_long) {

@@ -10,6 +10,19 @@
 
 namespace mi {
 
+// ---- the step-cost model shared by the plan rules ---------------------------------------------------------------------------------------------
+// Bytes a step moves under the gather model: every nonzero fetches its B row (4 N bytes) and its (column, value) pair (8), every row stores its C row.
+// Each rule divides it by a rate of its own (6 TB/s: a gather out of the fabric; 18: out of L2; ...).
+__host__ __device__ inline double gather_bytes(int64_t nnz, int32_t M, int32_t N)
+{
+    return (double)nnz * (4.0 * N + 8.0) + 4.0 * (double)M * N;
+}
+// B fits one XCD's L2 (4 K N <= 6 MiB): a gather is an L2 hit, not a trip to the fabric
+__host__ __device__ inline bool b_l2_resident(int64_t K, int32_t N)
+{
+    return 4.0 * (double)K * (double)N <= 6.0 * 1048576.0;
+}
+
 // ---- auto hub threshold of the default (exact-order) mode ------------------------------------------------------
 // Two kernels take rows in stored order: the segment kernel (one lane group per row, 32 gathers in flight: 47 ns per
 // nonzero of ONE row on an idle chip, 140-430 ns beside a rows kernel that saturates the fabric; but thousands of rows at
@@ -24,6 +37,7 @@ namespace mi {
 // trip to the fabric) the step runs at the L2's gather rate (18 TB/s) and a segment's nonzero costs ~30 ns beside the others, ~16 ns alone -- the
 // constants above price such a step 3x too long and its segments 5x too slow, and rows went to the hub kernel that were faster as segments.
 // The histogram comes from the same pass over row_ptr that finds the longest row; both plan builders use this function.
+// The hub kernel moves 16-byte parts of B rows: a B narrower than one part (N < 4) has no hubs -- its long rows stay single exact segments.
 constexpr int kHistN = 6;
 __host__ __device__ inline int32_t hist_threshold(int i) { return 256 << i; }
 struct LenHist {
@@ -32,9 +46,10 @@ struct LenHist {
 };
 __host__ __device__ inline int32_t resolve_hub_threshold(int64_t nnz, int32_t M, int32_t K, int32_t N, const unsigned long long *nnz_above, int32_t max_len)
 {
-    const double bytes = (double)nnz * (4.0 * N + 8.0) + 4.0 * (double)M * N;
-    const bool resident = 4.0 * (double)K * (double)N <= 6.0 * 1048576.0;
-    const double step = bytes / (resident ? 18e12 : 6e12);
+    if (N < 4) return INT32_MAX;
+    constexpr double kFabricRate = 6e12, kL2Rate = 18e12;      // bytes per second
+    const bool resident = b_l2_resident(K, N);
+    const double step = gather_bytes(nnz, M, N) / (resident ? kL2Rate : kFabricRate);
     // a segment's cost per nonzero beside a saturating rows kernel grows with the bytes per gather: ~140 ns at N = 32, ~270 at 128,
     // ~430 at 256 (am-shaped N = 256: spmm_chunks 0.88 ms for 2 048-nonzero rows, profiles/r03b_am_kernel_stats.csv)
     const double seg_ns = resident ? 30.0 : 100.0 + 1.3 * (double)(N < 256 ? N : 256);
@@ -77,7 +92,8 @@ __host__ __device__ inline int32_t resolve_medium_threshold(int32_t mthr_user, i
     else if (local_pct >= 95) m = 1024;       // banded / mesh: every row's B rows are its neighbours' -- the rows kernel keeps all but the longest (banded rows of
                                               // 300 - 700 nonzeros: 0.47 - 0.73 of the time at every width against 64 / 512)
     else if (local_pct >= 50) {
-        const double step = ((double)nnz * (4.0 * N + 8.0) + 4.0 * (double)M * N) / 6e12;
+        constexpr double kFabricRate = 6e12;
+        const double step = gather_bytes(nnz, M, N) / kFabricRate;
         if (N >= 128) { if (step >= 200e-6) m = 512; }
         else {
             const int64_t by_mean = 4 * mean_len;

@@ -1301,8 +1301,8 @@ def test_gpu_and_host_plan_builders_agree(device, oracle):
         for thr, split in ((0, 0), (100, 0), (0, 1), (100, 1)):    # auto and a low explicit threshold; hubs whole or in pieces
             res = {}
             for gpu_pre in (1, 0):
-                # ("col_strips" off: its auto rule looks at the column-locality sample, which only the device builder takes;
-                #  forced strip counts through both builders: test_column_strips_keep_every_bit)
+                # ("col_strips" off here: forced strip counts through both builders are test_column_strips_keep_every_bit's, and the auto rule --
+                #  with the plans built after it -- is the two inputs below)
                 C, op = run_spmm(device, ptr, idx, vals, B, options={"gpu_preprocess": gpu_pre, "long_row_threshold": thr,
                                                                     "long_row_chunk": 64, "split_long_rows": split, "col_strips": 1})
                 res[gpu_pre] = (C, {k: op.get_option(k) for k in ("n_chunks", "n_long_rows", "n_hub_rows", "n_medium_rows", "n_partial_slots",
@@ -1314,7 +1314,38 @@ def test_gpu_and_host_plan_builders_agree(device, oracle):
             assert np.array_equal(bits(res[1][0]), bits(res[0][0])), (name, thr, split)
             t = res[1][1]["long_row_threshold"]
             assert np.array_equal(bits(res[1][0]), bits(expected(oracle, ptr, idx, vals, B, split, t, 64))), (name, thr, split)
+    # default options, where a plan is built again after the strips are known: the hubs folded into stripped segments (test_column_strips_fold_hubs_whose_
+    # chains_hide_inside_the_strips), and rows up to 1 024 nonzeros kept in the rows kernel (a community-ordered graph of long rows whose columns do not ascend
+    # in the row, so no strips: protein-unsorted's shape at half its rows, scripts/regret.py)
+    fold = _strip_case(65536, 65536, 150, 350, seed=17, hubs=(3000, 3000, 2500))
+    keep_rows = tuple(a.numpy() for a in synth.csr_dcsbm_device(65536, 300 * 65536, 3000, "cpu", mean_comm=2048, seed=5, sort_cols=False))
+    for name, (ptr, idx), key, want in (("fold", fold, "long_row_threshold", 1 << 30), ("keep_rows", keep_rows, "medium_row_threshold", 1024)):
+        vals = synth.normal_f32(idx.size, 8)
+        B = synth.normal_f32((ptr.size - 1) * 128, 9).reshape(-1, 128)
+        res = {}
+        for gpu_pre in (1, 0):
+            C, op = run_spmm(device, ptr, idx, vals, B, options={"gpu_preprocess": gpu_pre})
+            res[gpu_pre] = (C, {k: op.get_option(k) for k in ("n_chunks", "n_long_rows", "n_hub_rows", "n_medium_rows", "max_row_nnz", "long_row_threshold",
+                                                              "medium_row_threshold", "segment_nnz", "n_col_strips", "col_strips_table_hash", "n_block_groups",
+                                                              "column_locality_pct", "n_launches")})
+        assert res[1][1][key] == want, (name, res[1][1])
+        assert res[1][1] == res[0][1], (name, res[1][1], res[0][1])
+        assert np.array_equal(bits(res[1][0]), bits(res[0][0])), name
+        assert np.array_equal(bits(res[1][0]), bits(oracle.spmm_omp(ptr, idx, vals, B))), name
 
+
+def test_narrow_b_keeps_rows_without_hub_rows(device, oracle):
+    """N < 4: the hub kernel moves 16-byte parts of B rows, so a B narrower than one part has no hub rows -- also in the plan built again to keep rows up to
+    512 nonzeros in the rows kernel (a community-ordered graph of mean degree >= 64 and 65 536 rows), whose hub threshold used to be resolved afresh."""
+    ptr, idx = (a.numpy() for a in synth.csr_dcsbm_device(65536, 300 * 65536, 3000, "cpu", mean_comm=2048, seed=5, sort_cols=False))
+    M = ptr.size - 1
+    vals = synth.normal_f32(idx.size, 31)
+    for N in (1, 2, 3):
+        B = synth.normal_f32(M * N, 32 + N).reshape(M, N)
+        C, op = run_spmm(device, ptr, idx, vals, B)
+        assert op.get_option("medium_row_threshold") == 512, N          # the rebuild that keeps rows happened
+        assert op.get_option("n_hub_rows") == 0 and op.get_option("long_row_threshold") == auto_hub_threshold(M, N, ptr), N
+        assert np.array_equal(bits(C), bits(expected(oracle, ptr, idx, vals, B))), N
 
 def test_unaligned_pointers_fall_back_cleanly(device, oracle):
     """B/C that are only 4-byte aligned cannot use the MFMA block path (it keeps the strict 16-byte rule): the rows
@@ -1569,7 +1600,7 @@ def test_column_strips_auto_rule_and_extra_destinations(device, oracle):
 
 def test_column_strips_fold_hubs_whose_chains_hide_inside_the_strips(device, oracle):
     """Where strips are in force and the hub threshold is the library's to choose, rows above it become stripped segments too when the longest row's
-    sub-chains hide inside the strips' launches (mi_spmm.hip preprocess_on_gpu: 100 ns per nonzero of the longest row against half of the stripped
+    sub-chains hide inside the strips' launches (mi_spmm.hip next_plan: 100 ns per nonzero of the longest row against half of the stripped
     step's estimate); a row too long for that keeps the hubs, and so does an explicit threshold.  Scheduling only: always the oracle's bits."""
     M = K = 65536
     N = 128
