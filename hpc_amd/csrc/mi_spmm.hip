@@ -461,7 +461,7 @@ static int side_stream(mi_spmm_handle *h, int i, hipStream_t s, hipStream_t *out
     return MI_SPMM_OK;
 }
 
-namespace { int resolve_tile_cols(const mi_spmm_handle *h, int32_t N, int64_t ldb); }
+namespace { int resolve_tile_cols(const mi_spmm_handle *h, int32_t N); }
 
 // Column strips of the exact segments (plan.hpp), after either plan builder: the rule's cheap gates first, then one pass over
 // the segments' columns (ascending? how many nonzeros?), then the S sub-segment tables.
@@ -476,7 +476,7 @@ static int plan_col_strips(mi_spmm_handle *h)
     int lpr = 1;
     while (lpr < (h->feat + V - 1) / V) lpr <<= 1;
     lpr = lpr < 8 ? 8 : (lpr > 64 ? 64 : lpr);
-    const int cap = resolve_tile_cols(h, h->feat, h->feat) / V;
+    const int cap = resolve_tile_cols(h, h->feat) / V;
     if (V == 4 && lpr > cap) lpr = cap;
     int tile = lpr * V;
     if (tile > h->feat) tile = h->feat;
@@ -1068,39 +1068,33 @@ void launch_rows_v2_bt(int bt, int pol, const RowsArgs &a, dim3 grid, hipStream_
     else if (bt == 128) launch_rows_v2_pol<LPR, 128>(pol, a, grid, s);
     else launch_rows_v2_pol<LPR, 256>(pol, a, grid, s);
 }
-template <int V, bool WIDE>
+// The default cache policy and 256-thread workgroups at a fixed depth: the dword and wide-address fallbacks (8 deep) and
+// "rows_unroll" = 16: sixteen gathers in flight per lane group (default cache policy, 256-thread workgroups only).  Half the round trips per row at two
+// thirds of the occupancy: -13 % ... +23 % by graph (profiles/r05_rows_unroll_ab.txt), so never the rule's choice; "autotune" tries it
+template <int V, int UNROLL, bool WIDE>
 void launch_rows_v2_fixed(int lpr, const RowsArgs &a, dim3 grid, hipStream_t s)
 {
     switch (lpr) {
-    case 8: hipLaunchKernelGGL((spmm_rows_v2<V, 8, 8, WIDE, 1, 256>), grid, dim3(256), 0, s, a); break;
-    case 16: hipLaunchKernelGGL((spmm_rows_v2<V, 16, 8, WIDE, 1, 256>), grid, dim3(256), 0, s, a); break;
-    case 32: hipLaunchKernelGGL((spmm_rows_v2<V, 32, 8, WIDE, 1, 256>), grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((spmm_rows_v2<V, 64, 8, WIDE, 1, 256>), grid, dim3(256), 0, s, a); break;
+    case 8: hipLaunchKernelGGL((spmm_rows_v2<V, 8, UNROLL, WIDE, 1, 256>), grid, dim3(256), 0, s, a); break;
+    case 16: hipLaunchKernelGGL((spmm_rows_v2<V, 16, UNROLL, WIDE, 1, 256>), grid, dim3(256), 0, s, a); break;
+    case 32: hipLaunchKernelGGL((spmm_rows_v2<V, 32, UNROLL, WIDE, 1, 256>), grid, dim3(256), 0, s, a); break;
+    default: hipLaunchKernelGGL((spmm_rows_v2<V, 64, UNROLL, WIDE, 1, 256>), grid, dim3(256), 0, s, a); break;
     }
 }
-// "rows_unroll" = 16: sixteen gathers in flight per lane group (default cache policy, 256-thread workgroups only).  Half the round trips per row at two
-// thirds of the occupancy: -13 % ... +23 % by graph (profiles/r05_rows_unroll_ab.txt), so never the rule's choice; "autotune" tries it
-void launch_rows_v2_deep(int lpr, const RowsArgs &a, dim3 grid, hipStream_t s)
+// deep: the 16-deep instance (16-byte narrow lanes, 256 threads, kPolNtStore only: rows_deep)
+void launch_rows_v2_any(bool vec4, bool wide, bool deep, int lpr, int bt, int pol, const RowsArgs &a, dim3 grid, hipStream_t s)
 {
-    switch (lpr) {
-    case 8: hipLaunchKernelGGL((spmm_rows_v2<4, 8, 16, false, 1, 256>), grid, dim3(256), 0, s, a); break;
-    case 16: hipLaunchKernelGGL((spmm_rows_v2<4, 16, 16, false, 1, 256>), grid, dim3(256), 0, s, a); break;
-    case 32: hipLaunchKernelGGL((spmm_rows_v2<4, 32, 16, false, 1, 256>), grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL((spmm_rows_v2<4, 64, 16, false, 1, 256>), grid, dim3(256), 0, s, a); break;
-    }
-}
-void launch_rows_v2_any(bool vec4, bool wide, int lpr, int bt, int pol, const RowsArgs &a, dim3 grid, hipStream_t s)
-{
-    if (vec4 && !wide) {
+    if (deep) launch_rows_v2_fixed<4, 16, false>(lpr, a, grid, s);
+    else if (vec4 && !wide) {
         switch (lpr) {
         case 8: launch_rows_v2_bt<8>(bt, pol, a, grid, s); break;
         case 16: launch_rows_v2_bt<16>(bt, pol, a, grid, s); break;
         case 32: launch_rows_v2_bt<32>(bt, pol, a, grid, s); break;
         default: launch_rows_v2_bt<64>(bt, pol, a, grid, s); break;
         }
-    } else if (vec4) launch_rows_v2_fixed<4, true>(lpr, a, grid, s);
-    else if (wide) launch_rows_v2_fixed<1, true>(lpr, a, grid, s);
-    else launch_rows_v2_fixed<1, false>(lpr, a, grid, s);
+    } else if (vec4) launch_rows_v2_fixed<4, 8, true>(lpr, a, grid, s);
+    else if (wide) launch_rows_v2_fixed<1, 8, true>(lpr, a, grid, s);
+    else launch_rows_v2_fixed<1, 8, false>(lpr, a, grid, s);
 }
 
 template <int V, int LPR, bool WIDE>
@@ -1113,7 +1107,7 @@ void launch_chunks(const ChunkArgs &a, dim3 grid, hipStream_t s, int deep)
     else hipLaunchKernelGGL((spmm_chunks<V, LPR, 8, WIDE>), grid, dim3(kBlockThreads), 0, s, a);
 }
 template <int V, bool WIDE>
-void launch_chunks_lpr(int lpr, const ChunkArgs &a, dim3 grid, hipStream_t s, int deep = 0)
+void launch_chunks_lpr(int lpr, const ChunkArgs &a, dim3 grid, hipStream_t s, int deep)
 {
     switch (lpr) {
     case 8: launch_chunks<V, 8, WIDE>(a, grid, s, deep); break;
@@ -1122,6 +1116,9 @@ void launch_chunks_lpr(int lpr, const ChunkArgs &a, dim3 grid, hipStream_t s, in
     default: launch_chunks<V, 64, WIDE>(a, grid, s, deep); break;
     }
 }
+// [vec4][wide]
+constexpr void (*kLaunchChunks[2][2])(int, const ChunkArgs &, dim3, hipStream_t, int) = {
+    {launch_chunks_lpr<1, false>, launch_chunks_lpr<1, true>}, {launch_chunks_lpr<4, false>, launch_chunks_lpr<4, true>}};
 
 template <int G, bool WIDE, bool RUN>
 void launch_block_items_g(int slab, const BlockArgs &a, dim3 grid, hipStream_t s, int bt)
@@ -1133,13 +1130,11 @@ void launch_block_items_g(int slab, const BlockArgs &a, dim3 grid, hipStream_t s
     else if (G == 1 && slab == 64) hipLaunchKernelGGL((spmm_block_items<1, 4, 1, WIDE, RUN>), grid, dim3(bt), 0, s, a);
     else if (G == 1) hipLaunchKernelGGL((spmm_block_items<1, 2, 1, WIDE, RUN>), grid, dim3(bt), 0, s, a);
 }
-// cls: 0 = list items, 1 = run items holding one piece, 2 = run items sharing their B rows between two pieces
-void launch_block_items(int slab, int cls, bool wide, const BlockArgs &a, dim3 grid, hipStream_t s, int bt)
-{
-    if (cls == 2) { if (wide) launch_block_items_g<2, true, true>(slab, a, grid, s, bt); else launch_block_items_g<2, false, true>(slab, a, grid, s, bt); }
-    else if (cls == 1) { if (wide) launch_block_items_g<1, true, true>(slab, a, grid, s, bt); else launch_block_items_g<1, false, true>(slab, a, grid, s, bt); }
-    else { if (wide) launch_block_items_g<1, true, false>(slab, a, grid, s, bt); else launch_block_items_g<1, false, false>(slab, a, grid, s, bt); }
-}
+// [cls][wide]; cls: 0 = list items, 1 = run items holding one piece, 2 = run items sharing their B rows between two pieces
+constexpr void (*kLaunchBlockItems[3][2])(int, const BlockArgs &, dim3, hipStream_t, int) = {
+    {launch_block_items_g<1, false, false>, launch_block_items_g<1, true, false>},
+    {launch_block_items_g<1, false, true>, launch_block_items_g<1, true, true>},
+    {launch_block_items_g<2, false, true>, launch_block_items_g<2, true, true>}};
 
 void launch_small_step(int lpr, int deep, const SmallStepArgs &a, dim3 grid, hipStream_t s)
 {
@@ -1178,9 +1173,8 @@ void launch_hub(int sw, bool excl, const HubArgs &a, dim3 grid, hipStream_t s)
 //       Infinity Cache's size) instead of 1 GiB (uniform N=1024: 20.3 -> 19.4 ms, N=256: 5.44 -> 4.79; R-MAT N=512: 10.3 -> 8.3; dense-ish: +6 %);
 //     N < 256 with hub rows (longest row > 64 x mean: R-MAT-like column reuse): 64 as well (R-MAT N=128: 2.09 -> 1.81 ms);
 //     else the whole row (uniform N=128: 2.40 at 128, 2.42 at 64, 2.57 at 32).
-int resolve_tile_cols(const mi_spmm_handle *h, int32_t N, int64_t ldb)
+int resolve_tile_cols(const mi_spmm_handle *h, int32_t N)
 {
-    (void)ldb;
     if (h->in_force.tile_cols > 0) return (int)h->in_force.tile_cols;
     if (h->local_pct < 0 || h->local_pct >= 95) return 256;
     if (h->local_pct >= 50) {
@@ -1211,331 +1205,398 @@ int pow2_ceil(int x)
     return p;
 }
 
-}  // namespace
-
-extern "C" {
-
-// One column part [col0, col0 + N) of the step: d_vin / d_vout / partials already point at column col0.
-// The MFMA block kernel works on the whole width and is launched with the first part only (full = the
-// caller's original pointers and width).
-struct FullView { const float *B; float *C; int32_t N; };
-
-static int run_part(mi_spmm_handle *h, const float *d_vin, int64_t ldb, float *d_vout, int64_t ldc, int32_t row_begin,
-                    int32_t row_end, hipStream_t s, int32_t N, int64_t col0, bool blocks_on, bool launch_blocks_here,
-                    const FullView &full, int *launches_out, bool record, const PeerOut &po_full)
+// narrow addressing: byte offset of any B element < 2^32, column index and
+// row pitch in bytes < 2^24 (one v_mad_u32_u24 per gathered row)
+bool narrow_addressing(const mi_spmm_handle *h, int64_t ldb, int32_t n)
 {
-    // the extra destinations as this column part sees them (the hub and block kernels address the full width: po_full)
-    PeerOut po = po_full;
-    for (int q = 0; q < po.n; ++q) po.p[q] += col0;
+    return (int64_t)h->num_cols <= (1 << 24) && ldb * 4 < (1 << 24) &&
+           ((int64_t)(h->num_cols > 0 ? h->num_cols - 1 : 0) * ldb + n) * 4 <= ((int64_t)1 << 32);
+}
+
+// The step as launch_set was given it.  The hub and block kernels address its full width: they are launched with the first column part only.
+struct Step {
+    const float *B; float *C; int32_t N; PeerOut po;     // the caller's pointers, width and extra destinations
+    int64_t ldb, ldc;
+    int32_t row_begin, row_end;
+    bool blocks_on;         // the MFMA block kernels can run on this call (alignment)
+    hipStream_t s;
+};
+
+// One column part [col0, col0 + N) of the step and its launch shape, computed once (make_part) and read by every role's launch.
+struct Part {
+    int64_t col0;
+    int32_t N;
+    const float *B; float *C; PeerOut po;                // the step's pointers moved to column col0
+    int V;                  // floats per lane: 4 or 1
+    bool vec4, wide;        // wide: beyond narrow addressing
+    int lpr, tile_w, col_tiles;
+    int bt, rpg;            // rows kernel: workgroup size, contiguous rows per lane group
+    int64_t nblk;           // rows kernel: workgroups per column tile
+    int flags, pol;
+};
+
+int make_part(const mi_spmm_handle *h, const Step &st, int64_t col0, int32_t N, Part *out)
+{
+    Part &p = *out;
+    p.col0 = col0;
+    p.N = N;
+    p.B = st.B + col0;
+    p.C = st.C + col0;
+    p.po = st.po;
+    for (int q = 0; q < p.po.n; ++q) p.po.p[q] += col0;
     const int32_t M = h->num_v;
     // 16 bytes per lane whenever a row holds at least one float4: global dwordx4 accesses only need dword
     // alignment, and a row whose width is not a multiple of 4 gets its last lane shifted back to column N - 4
     // (spmm_kernels.hpp).  Only N < 4 takes the dword path.  The MFMA block path keeps the strict 16-byte rule.
-    const bool vec4 = N >= 4;
-    const int V = vec4 ? 4 : 1;
-    // narrow addressing: byte offset of any B element < 2^32, column index and
-    // row pitch in bytes < 2^24 (one v_mad_u32_u24 per gathered row)
-    const bool wide = !((int64_t)h->num_cols <= (1 << 24) && ldb * 4 < (1 << 24) &&
-                        ((int64_t)(h->num_cols > 0 ? h->num_cols - 1 : 0) * ldb + N) * 4 <= ((int64_t)1 << 32));
-    int lpr = pow2_ceil((N + V - 1) / V);
+    p.vec4 = N >= 4;
+    p.V = p.vec4 ? 4 : 1;
+    p.wide = !narrow_addressing(h, st.ldb, N);
+    int lpr = pow2_ceil((N + p.V - 1) / p.V);
     if (lpr < 8) lpr = 8;
     if (lpr > 64) lpr = 64;
     // Wide B (N >= 256): the column tiles are swept one after the other (blockIdx.x runs fastest), so a tile's
     // working set is K rows x tile_cols x 4 B.  Narrower tiles keep that set nearer the Infinity Cache's size.
-    const int tile_cap = resolve_tile_cols(h, N, ldb) / V;
-    if (vec4 && lpr > tile_cap) lpr = tile_cap;
-    const int tile_w = lpr * V;
-    const int col_tiles = (N + tile_w - 1) / tile_w;
-    const int bt = (vec4 && !wide) ? (int)h->block_threads : kBlockThreads;
-    const int gpb = bt / lpr;
+    const int tile_cap = resolve_tile_cols(h, N) / p.V;
+    if (p.vec4 && lpr > tile_cap) lpr = tile_cap;
+    p.lpr = lpr;
+    p.tile_w = lpr * p.V;
+    p.col_tiles = (N + p.tile_w - 1) / p.tile_w;
+    p.bt = (p.vec4 && !p.wide) ? (int)h->block_threads : kBlockThreads;
+    const int gpb = p.bt / lpr;
     int rpb = (int)h->rows_per_block;
     // one row per lane group -- except narrow groups on very short rows (N <= 32, mean degree < 12), where a second
     // row per group lets the next row's pairs be fetched under the current row's few gathers (+3-6 %, profiles/r01_thresholds.txt)
     const bool short_rows = lpr == 8 && M > 0 && h->nnz / M < 12;
     if (rpb <= 0) rpb = short_rows ? 2 * gpb : gpb;
     if (rpb < gpb) rpb = gpb;
-    int rpg = rpb / gpb;          // contiguous rows per lane group, at most LPR - 1
-    if (rpg > lpr - 1) rpg = lpr - 1;
-    if (rpg < 1) rpg = 1;
-    rpb = rpg * gpb;
-    const int64_t nblk64 = ((int64_t)(row_end - row_begin) + rpb - 1) / rpb;
-    if (nblk64 > INT32_MAX || col_tiles > 65535) return MI_SPMM_EUNSUPPORTED;
+    p.rpg = rpb / gpb;          // contiguous rows per lane group, at most LPR - 1
+    if (p.rpg > lpr - 1) p.rpg = lpr - 1;
+    if (p.rpg < 1) p.rpg = 1;
+    rpb = p.rpg * gpb;
+    p.nblk = ((int64_t)(st.row_end - st.row_begin) + rpb - 1) / rpb;
+    if (p.nblk > INT32_MAX || p.col_tiles > 65535) return MI_SPMM_EUNSUPPORTED;
     // auto: measured neutral-to-positive everywhere except one whole-wave row and a single column
     // tile (N = 256), where interleaving rows over the XCDs is ~3 % faster (profiles/r01_sweep_*)
-    const bool remap = h->xcd_remap < 0 ? !(lpr == 64 && col_tiles == 1) : (h->xcd_remap != 0);
-    const int flags = (remap ? kFlagXcdRemap : 0) | (h->ftz ? kFlagFtz : 0);
-    const int pol = (h->nt_store ? kPolNtStore : 0) | (h->nt_stream ? kPolNtStream : 0);
-    int launches = 0;
+    const bool remap = h->xcd_remap < 0 ? !(lpr == 64 && p.col_tiles == 1) : (h->xcd_remap != 0);
+    p.flags = (remap ? kFlagXcdRemap : 0) | (h->ftz ? kFlagFtz : 0);
+    p.pol = (h->nt_store ? kPolNtStore : 0) | (h->nt_stream ? kPolNtStream : 0);
+    return MI_SPMM_OK;
+}
 
-    // ---- small steps: one launch, three roles (spmm_kernels.hpp spmm_small_step) -------------------------------------------------------------
-    // Eligible: the plain case of every role -- 16-byte lanes, narrow addressing, ONE column tile, no column strips, no split rows, no block groups, the
-    // default workgroup size.  auto ("fused_step" = 2): only steps whose bytes take under 0.2 ms at 6 TB/s -- there the launch boundaries and the fork are
-    // a third of the step and the rows role's lower occupancy (3 waves per SIMD, the hub role's footprint) costs nothing; longer steps keep their kernels.
-    {
-        const bool eligible = vec4 && !wide && col_tiles == 1 && launch_blocks_here && N == full.N && h->n_strips <= 1 && !h->split_long && h->n_blk_groups == 0 &&
-                              bt == kBlockThreads && pol == kPolNtStore && (h->n_long > 0 || h->n_chunks > 0) &&
-                              (int64_t)((full.N + 15) / 16) * h->n_long + (int64_t)h->n_chunks + nblk64 < (int64_t)INT32_MAX;
-        // auto: the step's bytes take under 0.1 ms, or its longest row's chain (3.2 ns per nonzero) outlasts them anyway (am-shaped): then the rows role's
-        // occupancy cannot matter.  (First rule, 0.2 ms: youtube-shaped kLen 32 -- 0.155 ms of bytes, a 75 us chain, 35 K rows workgroups -- lost 6 - 14 %.)
-        // (an L2-resident B -- 4 K N <= 6 MiB, ddi-shaped -- moves its bytes three times faster: priced as in plan.hpp resolve_hub_threshold)
-        constexpr double kFabricRate = 6e12, kL2Rate = 18e12;
-        const double t_bytes = gather_bytes(h->nnz, h->num_v, full.N) / (b_l2_resident(h->num_cols, full.N) ? kL2Rate : kFabricRate);
-        // (local columns: the rows kernel alone is fast and wants its occupancy -- 0.1 ms; columns anywhere: latency-bound whatever the occupancy -- 0.16 ms:
-        //  arxiv-community N = 128 loses 18 % fused, arxiv-rcm gains 16 %; youtube-community kLen 32 loses 14 %, youtube-shuffled gains 11 %)
-        const double t_fused = h->local_pct >= 50 ? 100e-6 : 160e-6;
-        // (a step that is ONE launch anyway -- one role only: ddi-shaped N = 256, every row a segment -- keeps that role's own kernel, which is the better
-        //  instance of it: segments 32 gathers deep instead of 16 at the small-step kernel's footprint; ddi-community kLen 256: 85.7 -> 79 us)
-        const int n_roles = ((h->n_long > 0 && range_has_hub(h, row_begin, row_end)) ? 1 : 0) + (h->n_chunks > 0 ? 1 : 0) + (h->n_rows_for_rows_kernel > 0 ? 1 : 0);
-        const int64_t fused_step = h->in_force.fused_step;
-        const bool want = fused_step == 1 || (fused_step == 2 && n_roles >= 2 && (t_bytes < t_fused || (double)h->max_row_nnz * 3.2e-9 > t_bytes));
-        h->last_fused = 0;
-        if (eligible && want) {
-            SmallStepArgs fa{};
-            const bool hubs_here = h->n_long > 0 && range_has_hub(h, row_begin, row_end);
-            if (hubs_here) {
-                fa.h.rows = h->d_long; fa.h.row_ptr = h->d_ptr; fa.h.col_idx = h->d_idx; fa.h.vals = h->d_val;
-                fa.h.B = full.B; fa.h.C = full.C; fa.h.ldb = ldb; fa.h.ldc = ldc; fa.h.n_hubs = h->n_long; fa.h.N = full.N;
-                fa.h.slices = (full.N + 15) / 16; fa.h.row_lo = row_begin; fa.h.row_hi = row_end; fa.h.flags = h->ftz ? kFlagFtz : 0; fa.h.po = po_full;
-                fa.hub_wgs = fa.h.slices * h->n_long;
-            }
-            if (h->n_chunks > 0) {
-                fa.c.chunks = h->d_chunks; fa.c.col_idx = h->d_idx; fa.c.vals = h->d_val; fa.c.B = d_vin; fa.c.partials = nullptr; fa.c.C = d_vout;
-                fa.c.ldb = ldb; fa.c.ldp = h->ldp; fa.c.ldc = ldc; fa.c.n_chunks = h->n_chunks; fa.c.N = N; fa.c.flags = flags;
-                fa.c.row_lo = row_begin; fa.c.row_hi = row_end; fa.c.po = po;
-                fa.seg_wgs = (h->n_chunks + kBlockThreads / lpr - 1) / (kBlockThreads / lpr);
-            }
-            fa.r.blk_flag = nullptr; fa.r.row_ptr = h->d_ptr; fa.r.col_idx = h->d_idx; fa.r.vals = h->d_val; fa.r.B = d_vin; fa.r.C = d_vout;
-            fa.r.ldb = ldb; fa.r.ldc = ldc; fa.r.row0 = row_begin; fa.r.M = row_end; fa.r.N = N; fa.r.rows_per_block = rpg;
-            fa.r.long_thr = (int32_t)h->medium_res; fa.r.nblk = (int)nblk64; fa.r.flags = flags; fa.r.po = po;
-            const int rows_wgs = h->n_rows_for_rows_kernel > 0 ? (int)nblk64 : 0;       // every row may belong to the first two roles (ddi-shaped graphs)
-            if (fa.hub_wgs + fa.seg_wgs + rows_wgs == 0) { *launches_out += 0; return MI_SPMM_OK; }
-            // Which of the first two roles leads the grid (workgroups start in blockIdx order): the one whose longest chain LASTS longest.  A hub row costs
-            // 3.2 ns per nonzero plus ~2 us of pipeline fill; a segment is one lane group's dependent gather chain, 47 ns per nonzero (30 out of an
-            // L2-resident B), and the longest segment is as long as the hub threshold allows.  arxiv- / youtube- / am-shaped: one hub row of 10^4 - 10^5
-            // nonzeros is the step -> hubs first; ddi- / collab-shaped: hub rows of 700 - 1 800 nonzeros (2 - 6 us) over 256 - 512-nonzero segments
-            // (12 - 24 us) that used to START behind two rounds of hub workgroups -> segments first.
-            {
-                const bool l2_b = b_l2_resident(h->num_cols, full.N);
-                const int64_t seg_max = h->long_thr > 0 && h->long_thr < (int64_t)h->max_row_nnz ? h->long_thr : (int64_t)h->max_row_nnz;
-                const double t_seg = (double)seg_max * (l2_b ? 30e-9 : 47e-9), t_hub = 2e-6 + (double)h->max_row_nnz * 3.2e-9;
-                const bool both = fa.hub_wgs > 0 && fa.seg_wgs > 0;
-                fa.seg_first = both && (h->fused_order == 2 || (h->fused_order == 0 && t_seg > t_hub)) ? 1 : 0;
-                h->last_seg_first = fa.seg_first;
-            }
-            dim3 fgrid((unsigned)(fa.hub_wgs + fa.seg_wgs + rows_wgs));
-            launch_small_step(lpr, (int)h->segment_unroll, fa, fgrid, s);
-            h->last_fused = 1;
-            if (record) { h->last_wide = 0; h->last_lpr = lpr; h->last_v = V; }
-            *launches_out += 1;
-            return (int)hipGetLastError();
-        }
-    }
+// ---- one argument builder per role, for the separate kernels and the small-step kernel alike ---------------------------------------------
 
-    // segment, hub, block and reduce kernels walk their whole tables and keep the rows of this call's range.
-    // The hub kernel goes first (its longest row is the step's longest dependent chain) and, like the block kernel,
-    // addresses the full width: it is launched with the first column part only.
-    if (h->n_long > 0 && !h->split_long && launch_blocks_here && range_has_hub(h, row_begin, row_end)) {
-        // the hub kernel moves 16-byte parts of B rows: its last part starts at column N - 4 (hub_threshold_for gives a narrower B no hubs)
-        if (full.N < 4) return MI_SPMM_EUNSUPPORTED;
-        HubArgs ha{};
-        ha.rows = h->d_long;
-        ha.row_ptr = h->d_ptr;
-        ha.col_idx = h->d_idx;
-        ha.vals = h->d_val;
-        ha.B = full.B;
-        ha.C = full.C;
-        ha.ldb = ldb;
-        ha.ldc = ldc;
-        ha.n_hubs = h->n_long;
-        ha.N = full.N;
-        ha.row_lo = row_begin;
-        ha.row_hi = row_end;
-        ha.flags = h->ftz ? kFlagFtz : 0;
-        ha.po = po_full;
-        // Slice width, when the caller leaves it to us: 32 columns per chain wave -- unless the longest row's chain alone
-        // (3.3 ns per nonzero) is more than half of what the whole step's bytes take at 6 TB/s, i.e. that one chain is the
-        // step: then 16, whose loaders put half as much through the LDS the chain wave reads from (am-shaped, N = 128:
-        // 0.84 -> 0.72 ms; where the hub rows are many rather than one long, 32 is faster: R-MAT N = 32 0.47 vs 0.56;
-        // profiles/r03_hub_experiments.txt)
-        int sw = (int)h->hub_slice;
-        bool excl = false;         // the chain-bound case: the hub workgroups keep their CUs to themselves (spmm_kernels.hpp EXCL)
-        if (sw <= 0) {
-            constexpr double kFabricRate = 6e12;
-            const double step_s = gather_bytes(h->nnz, h->num_v, full.N) / kFabricRate;
-            // (round 4, new chain loop: 16 and 32 are within 1-3 % of each other on chain-bound graphs up to N = 128; at N = 256 the 16 workgroups
-            //  of a row cost more than they save: am-shaped 1.164 -> 1.119 ms with 32; 64 loses everywhere it is the chain that counts)
-            const bool chain_bound = full.N <= 128 && (double)h->max_row_nnz * 3.3e-9 > 0.5 * step_s;
-            sw = (full.N <= 16 || chain_bound) ? 16 : 32;
-            // ... and only while the hub workgroups are few: each keeps a whole CU, and 184 hubs x 8 slices of them (am-community N = 128) held the chip
-            // until the last one had gone -- the rows kernel behind them started late: 0.43 -> 0.57 ms (profiles/r05_regret.md)
-            excl = chain_bound && (int64_t)((full.N + 15) / 16) * h->n_long <= 128;
-        }
-        const bool wide_hub = !((int64_t)h->num_cols <= (1 << 24) && ldb * 4 < (1 << 24) &&
-                                ((int64_t)(h->num_cols > 0 ? h->num_cols - 1 : 0) * ldb + full.N) * 4 <= ((int64_t)1 << 32));
-        const int slices = (full.N + sw - 1) / sw;
-        if ((int64_t)slices * h->n_long > INT32_MAX) return MI_SPMM_EUNSUPPORTED;
-        ha.slices = slices;
-        dim3 hgrid((unsigned)(slices * h->n_long));
-        hipStream_t hs = s;
-        {
-            const int fr = side_stream(h, 0, s, &hs);
-            if (fr != 0) return fr;
-        }
-        if (wide_hub) launch_hub<true>(sw, excl, ha, hgrid, hs); else launch_hub<false>(sw, excl, ha, hgrid, hs);
-        ++launches;
-    }
-    if (h->n_chunks > 0) {
-        ChunkArgs ca{};
-        ca.chunks = h->d_chunks;
-        ca.col_idx = h->d_idx;
-        ca.vals = h->d_val;
-        ca.B = d_vin;
-        ca.partials = h->d_partials + col0;
-        ca.C = d_vout;
-        ca.ldb = ldb;
-        ca.ldp = h->ldp;
-        ca.ldc = ldc;
-        ca.n_chunks = h->n_chunks;
-        ca.N = N;
-        ca.flags = flags;
-        ca.row_lo = row_begin;
-        ca.row_hi = row_end;
-        ca.po = po;
-        const int cgpb = kBlockThreads / lpr;  // the chunk kernel always runs 256-thread workgroups
-        dim3 cgrid((h->n_chunks + cgpb - 1) / cgpb, col_tiles);
-        // partial rows are ldp (multiple of 4) floats and hipMalloc-aligned, so only
-        // the B side decides the vector width here
-        // on side stream 1: a segment is one lane group's dependent chain (up to long_row_threshold nonzeros), and the rows
-        // kernel behind it in the same stream would wait for the longest one
-        hipStream_t cs = s;
-        {
-            const int fr = side_stream(h, 1, s, &cs);
-            if (fr != 0) return fr;
-        }
-        // column strips (plan.hpp): one launch per strip in stream order, each over its own sub-segment table; every strip but the last
-        // leaves the chains in the local C (plain stores, no extra destinations), the last one finishes them like an unstripped launch
-        const int n_strips = (h->d_strips && h->n_strips > 1) ? h->n_strips : 1;
-        for (int st = 0; st < n_strips; ++st) {
-            if (n_strips > 1) {
-                ca.chunks = h->d_strips + (size_t)st * (size_t)h->n_chunks;
-                const bool last = st == n_strips - 1;
-                ca.flags = flags | (last ? (po.n > 0 ? kFlagStripNoSkip : 0) : kFlagStripCarry);
-                if (!last) ca.po.n = 0; else ca.po = po;
-            }
-            const int deep = h->segment_unroll > 0 ? (int)h->segment_unroll : (n_strips > 1 ? 16 : 32);
-            if (vec4) { if (wide) launch_chunks_lpr<4, true>(lpr, ca, cgrid, cs); else launch_chunks_lpr<4, false>(lpr, ca, cgrid, cs, deep); }
-            else { if (wide) launch_chunks_lpr<1, true>(lpr, ca, cgrid, cs); else launch_chunks_lpr<1, false>(lpr, ca, cgrid, cs); }
-            ++launches;
-        }
-    }
+HubArgs hub_args(const mi_spmm_handle *h, const Step &st, int slices)
+{
+    HubArgs a{};
+    a.rows = h->d_long;
+    a.row_ptr = h->d_ptr;
+    a.col_idx = h->d_idx;
+    a.vals = h->d_val;
+    a.B = st.B;
+    a.C = st.C;
+    a.ldb = st.ldb;
+    a.ldc = st.ldc;
+    a.n_hubs = h->n_long;
+    a.N = st.N;
+    a.slices = slices;
+    a.row_lo = st.row_begin;
+    a.row_hi = st.row_end;
+    a.flags = h->ftz ? kFlagFtz : 0;
+    a.po = st.po;
+    return a;
+}
 
-    const bool remap_blocks = h->xcd_remap != 0;   // list is column-ordered: keep neighbours on one XCD
-    // the block kernel addresses the FULL width (this part may be narrower when split_cols peels a remainder)
-    const bool wide_full = !((int64_t)h->num_cols <= (1 << 24) && ldb * 4 < (1 << 24) &&
-                             ((int64_t)(h->num_cols > 0 ? h->num_cols - 1 : 0) * ldb + full.N) * 4 <= ((int64_t)1 << 32));
-    if (blocks_on && launch_blocks_here) {
-        BlockArgs ba{};
-        ba.col_idx = h->d_idx;
-        ba.vals = h->d_val;
-        ba.B = full.B;
-        ba.C = full.C;
-        ba.ldb = ldb;
-        ba.ldc = ldc;
-        ba.N = full.N;
-        ba.remap = remap_blocks ? 1 : 0;
-        ba.row_lo = row_begin;
-        ba.row_hi = row_end;
-        ba.po = po_full;
-        const int slab = block_slab_width(full.N), slabs = full.N / slab;
-        // pass p continues the fma chains pass p-1 left in C: stream order is the dependency
-        for (int pass = 0; pass < h->n_blk_passes; ++pass) {
-            for (int cls = 2; cls >= 0; --cls) {
-                int32_t n = h->blk_launch[pass][cls].n;
-                ba.items = h->d_blk_items + h->blk_launch[pass][cls].off;
-                if (n == 0) continue;
-                ba.n_items = n;
-                // one item per wave, and ONE wave per workgroup by default: items differ 4x in length (64 or 128 rows, one or two
-                // pieces), and a 4-wave workgroup holds its four wave slots until its longest item is done -- 1.38 of 2 possible
-                // waves per SIMD were resident against 1.80 with single-wave workgroups (profiles/r03_c4_item_timeline.txt)
-                const int wpw = (int)h->block_wg_waves;
-                dim3 bgrid((unsigned)((n + wpw - 1) / wpw), slabs);
-                launch_block_items(slab, cls, wide_full, ba, bgrid, s, 64 * wpw);
-                ++launches;
-            }
-        }
-    }
+ChunkArgs segment_args(const mi_spmm_handle *h, const Step &st, const Part &p)
+{
+    ChunkArgs a{};
+    a.chunks = h->d_chunks;
+    a.col_idx = h->d_idx;
+    a.vals = h->d_val;
+    a.B = p.B;
+    // (read only by split-row segments, slot >= 0: never in the small-step kernel, which split_long steps do not take)
+    a.partials = h->d_partials + p.col0;
+    a.C = p.C;
+    a.ldb = st.ldb;
+    a.ldp = h->ldp;
+    a.ldc = st.ldc;
+    a.n_chunks = h->n_chunks;
+    a.N = p.N;
+    a.flags = p.flags;
+    a.row_lo = st.row_begin;
+    a.row_hi = st.row_end;
+    a.po = p.po;
+    return a;
+}
 
+RowsArgs rows_args(const mi_spmm_handle *h, const Step &st, const Part &p)
+{
     RowsArgs a{};
     a.blk_flag = h->n_blk_groups > 0 ? h->d_blk_flag : nullptr;
     a.row_ptr = h->d_ptr;
     a.col_idx = h->d_idx;
     a.vals = h->d_val;
-    a.B = d_vin;
-    a.C = d_vout;
-    a.ldb = ldb;
-    a.ldc = ldc;
-    a.row0 = row_begin;
-    a.M = row_end;
-    a.N = N;
-    a.rows_per_block = rpg;
+    a.B = p.B;
+    a.C = p.C;
+    a.ldb = st.ldb;
+    a.ldc = st.ldc;
+    a.row0 = st.row_begin;
+    a.M = st.row_end;
+    a.N = p.N;
+    a.rows_per_block = p.rpg;
     // rows above the medium threshold were given to the segment or hub kernel -- except rows of block groups (of any
     // length up to the detection cap): when the block path cannot run on this call (pointers or pitches not 16-byte
     // aligned) the rows kernel takes exactly those rows as well (kFlagBlockFallback), nothing is computed twice
-    const bool blocks_fallback = h->n_blk_groups > 0 && !blocks_on;
+    const bool blocks_fallback = h->n_blk_groups > 0 && !st.blocks_on;
     a.long_thr = (int32_t)h->medium_res;
-    a.nblk = (int)nblk64;
-    a.flags = flags | (blocks_fallback ? kFlagBlockFallback : 0);
-    a.po = po;
-    dim3 grid((unsigned)nblk64, col_tiles);
-    // Gathers in flight per lane group, auto: 8 -- except where the rows kernel carries LONG rows one wave per row: banded columns (the only plans that keep
-    // rows of hundreds of nonzeros here: medium threshold 1 024), ONE whole-wave column tile (N = 193 ... 256: at N = 512 the second tile's wave shares the
-    // row's B rows and 16 gains nothing) and a mean degree >= 256.  Then a row is one wave's chain of round trips and 16 halves them: banded 300-700 rows
-    // 0.89 (band +-2048) / 0.90 (+-512), 600-1000 rows 0.93; mean degree 150 and below: 0.98 ... 1.06 (profiles/r05_banded_unroll_ab.jsonl)
-    const int64_t rows_unroll = h->in_force.rows_unroll;
-    const bool deep_rows = rows_unroll == 16 || (rows_unroll == 0 && h->local_pct >= 95 && lpr == 64 && col_tiles == 1 && h->medium_res >= 512 &&
-                                                    M > 0 && h->nnz / M >= 256);
-    h->last_rows_deep = deep_rows && vec4 && !wide && bt == kBlockThreads && pol == kPolNtStore ? 1 : 0;
-    // every row may already be owned by the segment, split and block paths: nothing left to launch
-    const bool rows_needed = !((blocks_on || h->n_blk_groups == 0) && h->n_rows_for_rows_kernel == 0);
-    if (!rows_needed) { /* skip */ }
-    else if (deep_rows && vec4 && !wide && bt == kBlockThreads && pol == kPolNtStore) launch_rows_v2_deep(lpr, a, grid, s);
-    else launch_rows_v2_any(vec4, wide, lpr, bt, pol, a, grid, s);
-    if (rows_needed) ++launches;
+    a.nblk = (int)p.nblk;
+    a.flags = p.flags | (blocks_fallback ? kFlagBlockFallback : 0);
+    a.po = p.po;
+    return a;
+}
 
-    if (h->n_long > 0 && h->split_long) {
-        ReduceArgs ra{};
-        ra.rows = h->d_long;
-        ra.partials = h->d_partials + col0;
-        ra.C = d_vout;
-        ra.ldp = h->ldp;
-        ra.ldc = ldc;
-        ra.n_long = h->n_long;
-        ra.N = N;
-        ra.flags = flags;
-        ra.row_lo = row_begin;
-        ra.row_hi = row_end;
-        ra.po = po;
-        const int64_t threads = (int64_t)h->n_long * ((N + V - 1) / V);
-        dim3 rgrid((unsigned)((threads + kBlockThreads - 1) / kBlockThreads));
-        hipStream_t cs = s;       // behind the segment kernel that produced the partial sums
-        {
-            const int fr = side_stream(h, 1, s, &cs);
-            if (fr != 0) return fr;
-        }
-        if (vec4) hipLaunchKernelGGL((spmm_reduce_chunks<4>), rgrid, dim3(kBlockThreads), 0, cs, ra);
-        else hipLaunchKernelGGL((spmm_reduce_chunks<1>), rgrid, dim3(kBlockThreads), 0, cs, ra);
-        ++launches;
+ReduceArgs reduce_args(const mi_spmm_handle *h, const Step &st, const Part &p)
+{
+    ReduceArgs a{};
+    a.rows = h->d_long;
+    a.partials = h->d_partials + p.col0;
+    a.C = p.C;
+    a.ldp = h->ldp;
+    a.ldc = st.ldc;
+    a.n_long = h->n_long;
+    a.N = p.N;
+    a.flags = p.flags;
+    a.row_lo = st.row_begin;
+    a.row_hi = st.row_end;
+    a.po = p.po;
+    return a;
+}
+
+// ---- one enqueue function per role, in run_part's order ----------------------------------------------------------------------------------
+
+// ---- small steps: one launch, three roles (spmm_kernels.hpp spmm_small_step) -------------------------------------------------------------
+// Eligible: the plain case of every role -- 16-byte lanes, narrow addressing, ONE column tile, no column strips, no split rows, no block groups, the
+// default workgroup size.  auto ("fused_step" = 2): only steps whose bytes take under 0.2 ms at 6 TB/s -- there the launch boundaries and the fork are
+// a third of the step and the rows role's lower occupancy (3 waves per SIMD, the hub role's footprint) costs nothing; longer steps keep their kernels.
+// false: nothing launched, the separate kernels take the step.
+bool enqueue_small_step(mi_spmm_handle *h, const Step &st, const Part &p, int *launches)
+{
+    const bool eligible = p.vec4 && !p.wide && p.col_tiles == 1 && p.N == st.N && h->n_strips <= 1 && !h->split_long && h->n_blk_groups == 0 &&
+                          p.bt == kBlockThreads && p.pol == kPolNtStore && (h->n_long > 0 || h->n_chunks > 0) &&
+                          (int64_t)((st.N + 15) / 16) * h->n_long + (int64_t)h->n_chunks + p.nblk < (int64_t)INT32_MAX;
+    if (!eligible) return false;
+    // auto: the step's bytes take under 0.1 ms, or its longest row's chain (3.2 ns per nonzero) outlasts them anyway (am-shaped): then the rows role's
+    // occupancy cannot matter.  (First rule, 0.2 ms: youtube-shaped kLen 32 -- 0.155 ms of bytes, a 75 us chain, 35 K rows workgroups -- lost 6 - 14 %.)
+    // (an L2-resident B -- 4 K N <= 6 MiB, ddi-shaped -- moves its bytes three times faster: priced as in plan.hpp resolve_hub_threshold)
+    constexpr double kFabricRate = 6e12, kL2Rate = 18e12;
+    const double t_bytes = gather_bytes(h->nnz, h->num_v, st.N) / (b_l2_resident(h->num_cols, st.N) ? kL2Rate : kFabricRate);
+    // (local columns: the rows kernel alone is fast and wants its occupancy -- 0.1 ms; columns anywhere: latency-bound whatever the occupancy -- 0.16 ms:
+    //  arxiv-community N = 128 loses 18 % fused, arxiv-rcm gains 16 %; youtube-community kLen 32 loses 14 %, youtube-shuffled gains 11 %)
+    const double t_fused = h->local_pct >= 50 ? 100e-6 : 160e-6;
+    const bool hubs_here = h->n_long > 0 && range_has_hub(h, st.row_begin, st.row_end);
+    // (a step that is ONE launch anyway -- one role only: ddi-shaped N = 256, every row a segment -- keeps that role's own kernel, which is the better
+    //  instance of it: segments 32 gathers deep instead of 16 at the small-step kernel's footprint; ddi-community kLen 256: 85.7 -> 79 us)
+    const int n_roles = (hubs_here ? 1 : 0) + (h->n_chunks > 0 ? 1 : 0) + (h->n_rows_for_rows_kernel > 0 ? 1 : 0);
+    const int64_t fused_step = h->in_force.fused_step;
+    const bool want = fused_step == 1 || (fused_step == 2 && n_roles >= 2 && (t_bytes < t_fused || (double)h->max_row_nnz * 3.2e-9 > t_bytes));
+    if (!want) return false;
+    SmallStepArgs fa{};
+    if (hubs_here) {
+        fa.h = hub_args(h, st, (st.N + 15) / 16);
+        fa.hub_wgs = fa.h.slices * h->n_long;
     }
-    if (record) {
-        h->last_wide = wide ? 1 : 0;
-        h->last_lpr = lpr;
-        h->last_v = V;
+    if (h->n_chunks > 0) {
+        fa.c = segment_args(h, st, p);
+        fa.seg_wgs = (h->n_chunks + kBlockThreads / p.lpr - 1) / (kBlockThreads / p.lpr);
+    }
+    fa.r = rows_args(h, st, p);
+    const int rows_wgs = h->n_rows_for_rows_kernel > 0 ? (int)p.nblk : 0;       // every row may belong to the first two roles (ddi-shaped graphs)
+    if (fa.hub_wgs + fa.seg_wgs + rows_wgs == 0) return false;       // (the separate kernels have nothing to launch either)
+    // Which of the first two roles leads the grid (workgroups start in blockIdx order): the one whose longest chain LASTS longest.  A hub row costs
+    // 3.2 ns per nonzero plus ~2 us of pipeline fill; a segment is one lane group's dependent gather chain, 47 ns per nonzero (30 out of an
+    // L2-resident B), and the longest segment is as long as the hub threshold allows.  arxiv- / youtube- / am-shaped: one hub row of 10^4 - 10^5
+    // nonzeros is the step -> hubs first; ddi- / collab-shaped: hub rows of 700 - 1 800 nonzeros (2 - 6 us) over 256 - 512-nonzero segments
+    // (12 - 24 us) that used to START behind two rounds of hub workgroups -> segments first.
+    {
+        const bool l2_b = b_l2_resident(h->num_cols, st.N);
+        const int64_t seg_max = h->long_thr > 0 && h->long_thr < (int64_t)h->max_row_nnz ? h->long_thr : (int64_t)h->max_row_nnz;
+        const double t_seg = (double)seg_max * (l2_b ? 30e-9 : 47e-9), t_hub = 2e-6 + (double)h->max_row_nnz * 3.2e-9;
+        const bool both = fa.hub_wgs > 0 && fa.seg_wgs > 0;
+        fa.seg_first = both && (h->fused_order == 2 || (h->fused_order == 0 && t_seg > t_hub)) ? 1 : 0;
+        h->last_seg_first = fa.seg_first;
+    }
+    dim3 fgrid((unsigned)(fa.hub_wgs + fa.seg_wgs + rows_wgs));
+    launch_small_step(p.lpr, (int)h->segment_unroll, fa, fgrid, st.s);
+    ++*launches;
+    return true;
+}
+
+int enqueue_hubs(mi_spmm_handle *h, const Step &st, const Part &p, int *launches)
+{
+    if (!(h->n_long > 0 && !h->split_long && p.col0 == 0 && range_has_hub(h, st.row_begin, st.row_end))) return MI_SPMM_OK;
+    // the hub kernel moves 16-byte parts of B rows: its last part starts at column N - 4 (hub_threshold_for gives a narrower B no hubs)
+    if (st.N < 4) return MI_SPMM_EUNSUPPORTED;
+    // Slice width, when the caller leaves it to us: 32 columns per chain wave -- unless the longest row's chain alone
+    // (3.3 ns per nonzero) is more than half of what the whole step's bytes take at 6 TB/s, i.e. that one chain is the
+    // step: then 16, whose loaders put half as much through the LDS the chain wave reads from (am-shaped, N = 128:
+    // 0.84 -> 0.72 ms; where the hub rows are many rather than one long, 32 is faster: R-MAT N = 32 0.47 vs 0.56;
+    // profiles/r03_hub_experiments.txt)
+    int sw = (int)h->hub_slice;
+    bool excl = false;         // the chain-bound case: the hub workgroups keep their CUs to themselves (spmm_kernels.hpp EXCL)
+    if (sw <= 0) {
+        constexpr double kFabricRate = 6e12;
+        const double step_s = gather_bytes(h->nnz, h->num_v, st.N) / kFabricRate;
+        // (round 4, new chain loop: 16 and 32 are within 1-3 % of each other on chain-bound graphs up to N = 128; at N = 256 the 16 workgroups
+        //  of a row cost more than they save: am-shaped 1.164 -> 1.119 ms with 32; 64 loses everywhere it is the chain that counts)
+        const bool chain_bound = st.N <= 128 && (double)h->max_row_nnz * 3.3e-9 > 0.5 * step_s;
+        sw = (st.N <= 16 || chain_bound) ? 16 : 32;
+        // ... and only while the hub workgroups are few: each keeps a whole CU, and 184 hubs x 8 slices of them (am-community N = 128) held the chip
+        // until the last one had gone -- the rows kernel behind them started late: 0.43 -> 0.57 ms (profiles/r05_regret.md)
+        excl = chain_bound && (int64_t)((st.N + 15) / 16) * h->n_long <= 128;
+    }
+    const int slices = (st.N + sw - 1) / sw;
+    if ((int64_t)slices * h->n_long > INT32_MAX) return MI_SPMM_EUNSUPPORTED;
+    hipStream_t hs;
+    if (const int fr = side_stream(h, 0, st.s, &hs)) return fr;
+    dim3 hgrid((unsigned)(slices * h->n_long));
+    (narrow_addressing(h, st.ldb, st.N) ? launch_hub<false> : launch_hub<true>)(sw, excl, hub_args(h, st, slices), hgrid, hs);
+    ++*launches;
+    return MI_SPMM_OK;
+}
+
+int enqueue_segments(mi_spmm_handle *h, const Step &st, const Part &p, int *launches)
+{
+    if (h->n_chunks <= 0) return MI_SPMM_OK;
+    ChunkArgs ca = segment_args(h, st, p);
+    const int cgpb = kBlockThreads / p.lpr;  // the chunk kernel always runs 256-thread workgroups
+    dim3 cgrid((h->n_chunks + cgpb - 1) / cgpb, p.col_tiles);
+    // partial rows are ldp (multiple of 4) floats and hipMalloc-aligned, so only
+    // the B side decides the vector width here
+    // on side stream 1: a segment is one lane group's dependent chain (up to long_row_threshold nonzeros), and the rows
+    // kernel behind it in the same stream would wait for the longest one
+    hipStream_t cs;
+    if (const int fr = side_stream(h, 1, st.s, &cs)) return fr;
+    // column strips (plan.hpp): one launch per strip in stream order, each over its own sub-segment table; every strip but the last
+    // leaves the chains in the local C (plain stores, no extra destinations), the last one finishes them like an unstripped launch
+    const int n_strips = (h->d_strips && h->n_strips > 1) ? h->n_strips : 1;
+    for (int strip = 0; strip < n_strips; ++strip) {
+        if (n_strips > 1) {
+            ca.chunks = h->d_strips + (size_t)strip * (size_t)h->n_chunks;
+            const bool last = strip == n_strips - 1;
+            ca.flags = p.flags | (last ? (p.po.n > 0 ? kFlagStripNoSkip : 0) : kFlagStripCarry);
+            if (!last) ca.po.n = 0; else ca.po = p.po;
+        }
+        const int deep = h->segment_unroll > 0 ? (int)h->segment_unroll : (n_strips > 1 ? 16 : 32);
+        kLaunchChunks[p.vec4][p.wide](p.lpr, ca, cgrid, cs, deep);
+        ++*launches;
+    }
+    return MI_SPMM_OK;
+}
+
+int enqueue_block_passes(mi_spmm_handle *h, const Step &st, const Part &p, int *launches)
+{
+    if (!(st.blocks_on && p.col0 == 0)) return MI_SPMM_OK;
+    const bool remap_blocks = h->xcd_remap != 0;   // list is column-ordered: keep neighbours on one XCD
+    // the block kernel addresses the FULL width (this part may be narrower when split_cols peels a remainder)
+    const bool wide_full = !narrow_addressing(h, st.ldb, st.N);
+    BlockArgs ba{};
+    ba.col_idx = h->d_idx;
+    ba.vals = h->d_val;
+    ba.B = st.B;
+    ba.C = st.C;
+    ba.ldb = st.ldb;
+    ba.ldc = st.ldc;
+    ba.N = st.N;
+    ba.remap = remap_blocks ? 1 : 0;
+    ba.row_lo = st.row_begin;
+    ba.row_hi = st.row_end;
+    ba.po = st.po;
+    const int slab = block_slab_width(st.N), slabs = st.N / slab;
+    // pass p continues the fma chains pass p-1 left in C: stream order is the dependency
+    for (int pass = 0; pass < h->n_blk_passes; ++pass) {
+        for (int cls = 2; cls >= 0; --cls) {
+            int32_t n = h->blk_launch[pass][cls].n;
+            ba.items = h->d_blk_items + h->blk_launch[pass][cls].off;
+            if (n == 0) continue;
+            ba.n_items = n;
+            // one item per wave, and ONE wave per workgroup by default: items differ 4x in length (64 or 128 rows, one or two
+            // pieces), and a 4-wave workgroup holds its four wave slots until its longest item is done -- 1.38 of 2 possible
+            // waves per SIMD were resident against 1.80 with single-wave workgroups (profiles/r03_c4_item_timeline.txt)
+            const int wpw = (int)h->block_wg_waves;
+            dim3 bgrid((unsigned)((n + wpw - 1) / wpw), slabs);
+            kLaunchBlockItems[cls][wide_full](slab, ba, bgrid, st.s, 64 * wpw);
+            ++*launches;
+        }
+    }
+    return MI_SPMM_OK;
+}
+
+// Gathers in flight per lane group, auto: 8 -- except where the rows kernel carries LONG rows one wave per row: banded columns (the only plans that keep
+// rows of hundreds of nonzeros here: medium threshold 1 024), ONE whole-wave column tile (N = 193 ... 256: at N = 512 the second tile's wave shares the
+// row's B rows and 16 gains nothing) and a mean degree >= 256.  Then a row is one wave's chain of round trips and 16 halves them: banded 300-700 rows
+// 0.89 (band +-2048) / 0.90 (+-512), 600-1000 rows 0.93; mean degree 150 and below: 0.98 ... 1.06 (profiles/r05_banded_unroll_ab.jsonl)
+bool rows_deep(const mi_spmm_handle *h, const Part &p)
+{
+    const int32_t M = h->num_v;
+    const int64_t rows_unroll = h->in_force.rows_unroll;
+    const bool deep_rows = rows_unroll == 16 || (rows_unroll == 0 && h->local_pct >= 95 && p.lpr == 64 && p.col_tiles == 1 && h->medium_res >= 512 &&
+                                                    M > 0 && h->nnz / M >= 256);
+    return deep_rows && p.vec4 && !p.wide && p.bt == kBlockThreads && p.pol == kPolNtStore;
+}
+
+int enqueue_rows(mi_spmm_handle *h, const Step &st, const Part &p, int *launches)
+{
+    // every row may already be owned by the segment, split and block paths: nothing left to launch
+    if ((st.blocks_on || h->n_blk_groups == 0) && h->n_rows_for_rows_kernel == 0) return MI_SPMM_OK;
+    dim3 grid((unsigned)p.nblk, p.col_tiles);
+    launch_rows_v2_any(p.vec4, p.wide, rows_deep(h, p), p.lpr, p.bt, p.pol, rows_args(h, st, p), grid, st.s);
+    ++*launches;
+    return MI_SPMM_OK;
+}
+
+int enqueue_reduce(mi_spmm_handle *h, const Step &st, const Part &p, int *launches)
+{
+    if (!(h->n_long > 0 && h->split_long)) return MI_SPMM_OK;
+    const int64_t threads = (int64_t)h->n_long * ((p.N + p.V - 1) / p.V);
+    dim3 rgrid((unsigned)((threads + kBlockThreads - 1) / kBlockThreads));
+    hipStream_t cs;       // behind the segment kernel that produced the partial sums
+    if (const int fr = side_stream(h, 1, st.s, &cs)) return fr;
+    const ReduceArgs ra = reduce_args(h, st, p);
+    if (p.vec4) hipLaunchKernelGGL((spmm_reduce_chunks<4>), rgrid, dim3(kBlockThreads), 0, cs, ra);
+    else hipLaunchKernelGGL((spmm_reduce_chunks<1>), rgrid, dim3(kBlockThreads), 0, cs, ra);
+    ++*launches;
+    return MI_SPMM_OK;
+}
+
+// One column part [col0, col0 + N) of the step: the small-step kernel, or the roles' own kernels.  Segment, hub, block and reduce kernels walk
+// their whole tables and keep the rows of this call's range; the hub kernel goes first (its longest row is the step's longest dependent chain).
+// The first part records the step's diagnostics.
+int run_part(mi_spmm_handle *h, const Step &st, int64_t col0, int32_t N, int *launches_out)
+{
+    Part p;
+    int rc = make_part(h, st, col0, N, &p);
+    if (rc != MI_SPMM_OK) return rc;
+    int launches = 0;
+    const bool fused = col0 == 0 && enqueue_small_step(h, st, p, &launches);
+    if (!fused) {
+        rc = enqueue_hubs(h, st, p, &launches);
+        if (rc == MI_SPMM_OK) rc = enqueue_segments(h, st, p, &launches);
+        if (rc == MI_SPMM_OK) rc = enqueue_block_passes(h, st, p, &launches);
+        if (rc == MI_SPMM_OK) rc = enqueue_rows(h, st, p, &launches);
+        if (rc == MI_SPMM_OK) rc = enqueue_reduce(h, st, p, &launches);
+        if (rc != MI_SPMM_OK) return rc;
+    }
+    if (col0 == 0) {
+        h->last_fused = fused ? 1 : 0;
+        h->last_rows_deep = !fused && rows_deep(h, p) ? 1 : 0;      // (the small-step kernel's rows role is 8 deep)
+        h->last_wide = p.wide ? 1 : 0;
+        h->last_lpr = p.lpr;
+        h->last_v = p.V;
     }
     *launches_out += launches;
     return (int)hipGetLastError();
 }
 
-}  // extern "C"  (run_part is internal)
+}  // namespace
 
 extern "C" {
 
@@ -1580,7 +1641,7 @@ static int launch_set(mi_spmm_handle *h, const float *d_vin, int64_t ldb, float 
                      (((uintptr_t)d_vin | (uintptr_t)d_vout) & 15u) == 0;
     for (int q = 0; q < n_extra; ++q) aligned16 = aligned16 && ((uintptr_t)d_extra[q] & 15u) == 0;
     const bool blocks_on = h->n_blk_groups > 0 && aligned16;
-    const FullView full = {d_vin, d_vout, N};
+    const Step st = {d_vin, d_vout, N, po, ldb, ldc, row_begin, row_end, blocks_on, s};
     // Widths just above a multiple of 256: the last 256-column tile would hold only a few columns yet run one
     // row per wave.  Up to 64 such columns go to a second set of launches with their own, narrower lane groups:
     // N = 257 / 260: -7 % time; wider remainders measured neutral, so they stay tiles of the one launch
@@ -1589,10 +1650,8 @@ static int launch_set(mi_spmm_handle *h, const float *d_vin, int64_t ldb, float 
     if (rem > 64) rem = 0;
     int launches = 0;
     h->fork_recorded = h->forked[0] = h->forked[1] = false;
-    int rc = run_part(h, d_vin, ldb, d_vout, ldc, row_begin, row_end, s, N - rem, 0, blocks_on, true, full, &launches, true, po);
-    if (rc == 0 && rem > 0)
-        rc = run_part(h, d_vin + (N - rem), ldb, d_vout + (N - rem), ldc, row_begin, row_end, s, rem, N - rem, blocks_on,
-                      false, full, &launches, false, po);
+    int rc = run_part(h, st, 0, N - rem, &launches);
+    if (rc == 0 && rem > 0) rc = run_part(h, st, N - rem, rem, &launches);
     for (int i = 0; i < 2; ++i) {      // join: whatever the caller enqueues next is ordered after the side streams' rows too
         if (!h->forked[i]) continue;
         h->forked[i] = false;

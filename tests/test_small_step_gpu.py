@@ -65,6 +65,13 @@ def test_small_step_gives_the_separate_kernels_bits(device, oracle, N):
         got = d_C.cpu().numpy()
         assert np.array_equal(bits(got[:, :N]), bits(exp)), (N, fused, ranges, int((bits(got[:, :N]) != bits(exp)).sum()))
         assert np.isnan(got[:, N:]).all()
+    # the small-step kernel's rows role is 8 gathers deep whatever "rows_unroll" says -- also right after a 16-deep rows launch on the handle
+    op.set_option("rows_unroll", 16)
+    for fused in (0, 1):
+        op.set_option("fused_step", fused)
+        op.run_ld(d_B, ldb, d_C, ldc)
+    torch.cuda.synchronize()
+    assert (op.get_option("fused_step_in_force"), op.get_option("rows_unroll_in_force")) == (1, 8), N
 
 
 def test_small_step_roles_may_be_absent_and_ineligible_steps_keep_their_kernels(device, oracle):
